@@ -21,7 +21,15 @@ device matrix, sit in registers — DESIGN.md §1).  Beside it:
     vectors (MODE 2);
   * validation: the lowest Ritz value of the last timed run's tridiagonal
     against the committed oracle E0 (tests/golden/c2_e0.json) at 1e-10.
-Sections (rank 0 prints, all ranks take part):
+A plain run (`--gpus N --steps K --warmup W`) sets up the sector, warms up,
+times the K steps and prints the headline line (value, ms_per_step); with
+`--dump-outputs DIR` it also writes what the last timed step returned — the
+Lanczos alpha and beta of that run — as DIR/alpha.npy and DIR/beta.npy
+(float64; ranks above 0 write alpha_rank<r>.npy / beta_rank<r>.npy).  The
+inputs (seeded bath, fixed start vector) are the same from run to run.
+Everything listed "beside it" above and the sections below run only with
+`--full`, which prints the long line.
+Sections (`--full`; rank 0 prints, all ranks take part):
   * farm_c4 (configs[3]), nonsu2_c5 (configs[4]) — asserted against the
     committed oracle fixtures tests/golden/c4_diag_random.json /
     c5_gf_random.npz;
@@ -688,19 +696,59 @@ def north_star_scalars(out, mode2_ips, direct_ips, cplx_ips, cplxh_ips):
     }
 
 
+def dump_outputs(dirname, rank, last):
+    """`--dump-outputs DIR`: what the last timed step returned to its caller
+    (lanc_run's alpha and beta, float64), one .npy per array."""
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    for name, arr in (("alpha", last[0]), ("beta", last[1])):
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
+def headline(args, world, value, dt, dev_ms, mode):
+    """The result line's headline fields (every run prints these)."""
+    return {
+        "metric": "Lanczos SpMV GB/s + ground-state iters/s, Ns=16 half-filled sector, 1/2/4/8 GPU",
+        "value": round(value, 1),
+        "unit": "Lanczos iters/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (seeded random bath per rank)",
+        "config": {"workload": "c2: Norb=1 Nbath=7 (Nlevels=16) half-filled (4,4) sector, dim 4900, "
+                               f"stored real(8) H, plain Lanczos {args.niter} iters/step, persistent MODE "
+                               f"{mode} (4 = stored matrix in the Kronecker register layout)",
+                   "parallelism": f"sector replicas x{world}"},
+        "device_ms_per_step": round(dev_ms / args.steps, 4),
+        "full": bool(args.full),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--niter", type=int, default=512)
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-farm", action="store_true", help="skip the configs[3]/[4] sections")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's alpha and beta as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the validation, the other arithmetic, the roofline, "
+                         "farm and CPU-baseline sections (the long line)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline sections")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-farm", action="store_true", help="with --full: skip the configs[3]/[4] sections")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
     if args.launch_check:
@@ -732,6 +780,12 @@ def main():
     from edgpu.hamiltonian import Sector
     from edgpu.params import make_config
     from golden.golden_configs import SEED, c2_config
+
+    def finish():
+        S.close()
+        if dist:
+            tdist.barrier()
+            tdist.destroy_process_group()
 
     seed = SEED + rank
     cfg = c2_config("random", seed)
@@ -765,6 +819,12 @@ def main():
         dt = float(t.item())
     iters_total = args.steps * args.niter * world
     value = iters_total / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, last)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, value, dt, dev_ms, mode)))
+        return finish()
 
     # validation of the timed work: lowest Ritz value of the last run's
     # tridiagonal vs the oracle's E0 for this rank's bath (committed fixture)
@@ -808,24 +868,8 @@ def main():
         roof, kron = roof_kron
         # the CPU baseline is a rank-0, N=1 measurement (task contract)
         cpu = None if (args.no_cpu or world > 1) else cpu_baseline()
-        out = {
-            "metric": "Lanczos SpMV GB/s + ground-state iters/s, Ns=16 half-filled sector, 1/2/4/8 GPU",
-            "value": round(value, 1),
-            "unit": "Lanczos iters/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (seeded random bath per rank)",
-            "config": {"workload": "c2: Norb=1 Nbath=7 (Nlevels=16) half-filled (4,4) sector, dim 4900, "
-                                   f"stored real(8) H, plain Lanczos {args.niter} iters/step, persistent MODE "
-                                   f"{mode} (4 = stored matrix in the Kronecker register layout)",
-                       "parallelism": f"sector replicas x{world}"},
-            "device_ms_per_step": round(dev_ms / args.steps, 4),
+        out = headline(args, world, value, dt, dev_ms, mode)
+        out.update({
             "validation": valid,
             "stored_mode2_note": "configs[1]: stored SELL matrix as ELL words {col|value} in registers (MODE 2)",
             "direct_note": f"configs[2]: same sector, matrix-free hop tables (persistent MODE {direct_mode})",
@@ -844,13 +888,10 @@ def main():
             "split_n28": split,
             "nonsu2_c5": nonsu2,
             "farm_c4": farm,
-        }
+        })
         out.update(north_star_scalars(out, mode2_ips, direct_ips, cplx_ips, cplxh_ips))
         print(json.dumps(out))
-    S.close()
-    if dist:
-        tdist.barrier()
-        tdist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

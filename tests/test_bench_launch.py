@@ -49,10 +49,35 @@ def test_launch_rejects_world_mismatch():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_one_gpu():
-    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--niter", "256", "--no-roofline", "--no-cpu"],
-               env_extra={"ED_BENCH_BACKEND": "gloo", "ED_BENCH_ONE_DEVICE": "1"}, timeout=600)
+    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--niter", "256", "--full", "--no-roofline",
+                "--no-cpu"], env_extra={"ED_BENCH_BACKEND": "gloo", "ED_BENCH_ONE_DEVICE": "1"}, timeout=600)
     assert out["n_gpus"] == 2
     assert out["validation"]["rel_dev"] < 1e-10
     assert out["farm_c4"]["n_gpus"] == 2 and out["farm_c4"]["parity"]["E0_rel_dev"] < 1e-10
     assert out["nonsu2_c5"]["parity"]["G_iw_max_rel_dev"] < 1e-10
     assert out["split_n28"]["backend"] == "gloo"
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run prints the headline line only (no --full section) and
+    `--dump-outputs` writes the last timed step's alpha and beta: float64,
+    one entry per iteration, lowest Ritz value = the oracle E0 of the seeded
+    bath (tests/golden/c2_e0.json) at 1e-10."""
+    import numpy as np
+    from scipy.linalg import eigh_tridiagonal
+
+    from golden.golden_configs import SEED
+
+    d = tmp_path / "out"
+    out = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+    assert out["steps"] == 3 and out["n_gpus"] == 1 and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] * 1e-3 / 512 - 1) < 1e-3
+    assert not {"validation", "roofline", "farm_c4", "cpu_baseline", "nonsu2_c5"} & set(out)
+    assert sorted(p.name for p in d.iterdir()) == ["alpha.npy", "beta.npy"]
+    a, b = np.load(d / "alpha.npy"), np.load(d / "beta.npy")
+    assert a.dtype == np.float64 and b.dtype == np.float64 and a.shape == b.shape == (512,)
+    ritz = eigh_tridiagonal(a, b[1:], eigvals_only=True, select="i", select_range=(0, 0))[0]
+    with open(os.path.join(ROOT, "tests", "golden", "c2_e0.json")) as fh:
+        e0 = json.load(fh)["by_seed"][str(SEED)]["E0"]
+    assert abs(ritz - e0) / abs(e0) < 1e-10

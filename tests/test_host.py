@@ -48,10 +48,10 @@ def test_dimensions_and_sectors():
     assert sum(s.dim for s in setup_pointers(cfg)) == 2 ** (2 * cfg.Ns)
 
 
-def test_params_struct_layout():
+def test_params_struct_layout(tmp_path):
     """ctypes mirror matches the C struct size computed by the C compiler."""
     src = '#include "%s"\n#include <stdio.h>\nint main(){printf("%%zu",sizeof(ed_params));}' % HEADER
-    exe = "/tmp/_edp_size"
+    exe = str(tmp_path / "edp_size")
     subprocess.run(["gcc", "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
     size = int(subprocess.run([exe], capture_output=True, text=True, check=True).stdout)
     assert size == ctypes.sizeof(EdParams)

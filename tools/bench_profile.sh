@@ -4,7 +4,8 @@
 # them.  Per (kernel, grid) group the bench's 5 warm-up launches are dropped
 # (tools/trace_summary.py), so each sector's steady-state average sits beside
 # the line's HIP-event `ms_per_launch`.
-#   bash tools/bench_profile.sh TAG [bench.py arguments]
+#   bash tools/bench_profile.sh TAG --full [further bench.py arguments]
+# (the roofline loops run only under bench.py --full)
 # -> gpurun_out/bprof_TAG/profiles/ (merged back by gpurun; copy to
 #    profiles/TAG): bench_kernel_stats.csv, bench_trace_{spmv,spmv_cplx,kron,direct}.json
 set -o pipefail
