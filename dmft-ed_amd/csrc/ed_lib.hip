@@ -30,6 +30,7 @@
 #include "ed_split.hpp"
 #include "ed_tables.hpp"
 #include "ed_host.hpp"
+#include "ed_hosteig.hpp"
 
 using namespace edg;
 
@@ -40,9 +41,7 @@ std::string& ed_err_slot() {
   return e;
 }
 
-static constexpr int kMaxGrid = 65536;
-// columns of the thick-restart coefficient buffers (ncv + probe columns)
-static constexpr int kTrlanMaxCols = 64;  // one thread per row up to 16.7 M rows
+static constexpr int kMaxGrid = 65536;  // one thread per row up to 16.7 M rows
 static inline int grid_for(int64_t nthreads) {
   int64_t b = (nthreads + kBlock - 1) / kBlock;
   return (int)std::max<int64_t>(1, std::min<int64_t>(b, kMaxGrid));
@@ -239,10 +238,13 @@ static int upload(ed_sector* s, T** p, const std::vector<T>& h) {
   return dcopy(s, *p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
-// Pinned host staging (Lanczos alpha|beta copies) from a process-wide pool
-// that only grows: hipHostFree / hipHostMalloc synchronise the device, which
-// would stall every other worker thread's stream (and break their graph
-// captures) each time a sector is closed or resized.
+// Pinned host staging, every buffer of the library (a sector's plain-Lanczos
+// alpha|beta copies; the thick-restart, batch and lockstep solves' per-call
+// staging through PinnedLease), from a process-wide pool that only grows:
+// hipHostFree / hipHostMalloc synchronise the device, which would stall every
+// other worker thread's stream (and break their graph captures), so nothing
+// is freed while the library is in use.  Blocks belong to no host thread:
+// short-lived threads (a farm call's workers) leak none.
 static std::mutex g_pin_mu;
 static std::multimap<size_t, void*> g_pin_free;  // free blocks by size
 static std::map<void*, size_t> g_pin_size;       // every block ever allocated
@@ -268,6 +270,27 @@ static void pinned_put(void* p) {
   std::lock_guard<std::mutex> lk(g_pin_mu);
   g_pin_free.emplace(g_pin_size[p], p);
 }
+// A pool block for one solve on stream st, returned only once st is idle (it
+// is on the success path; after an early error return a copy may still be in
+// flight, and the block must not reach another thread under it).
+struct PinnedLease {
+  void* const p;
+  const hipStream_t st;
+  PinnedLease(size_t n, hipStream_t st_) : p(pinned_get(n)), st(st_) {}
+  PinnedLease(const PinnedLease&) = delete;
+  ~PinnedLease() {
+    if (!p) return;
+    (void)hipStreamSynchronize(st);
+    pinned_put(p);
+  }
+};
+struct DevFree {  // hipFreeAsync of one device block at scope exit
+  void* p;
+  hipStream_t st;
+  ~DevFree() { (void)hipFreeAsync(p, st); }
+};
+// sub-arrays of a device slice of doubles start on 16-byte boundaries (double2)
+static inline size_t even(size_t q) { return (q + 1) & ~(size_t)1; }
 
 static void sector_free(ed_sector* s) {
   if (!s) return;
@@ -1735,11 +1758,7 @@ sized:
 __global__ void k_default_start(double* v, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kBlock) {
-    uint64_t z = (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
-    v[i] = (double)(z >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
+    v[i] = splitmix_unit((uint64_t)(i + 1));
   }
 }
 
@@ -2280,240 +2299,11 @@ static int persist_set_thresh(ed_sector* s, double thresh, hipStream_t st) {
   return ED_OK;
 }
 
-// Host tridiagonal eigen-solver (tql2, EISPACK; the same algorithm the
-// reference uses for Ritz values, .repo/PLAIN_LANCZOS.f90:427-565).
-static double pythag(double a, double b) {
-  double p = std::max(fabs(a), fabs(b));
-  if (p != 0.0) {
-    double r = std::min(fabs(a), fabs(b)) / p;
-    r = r * r;
-    for (;;) {
-      double t = 4.0 + r;
-      if (t == 4.0) break;
-      double s = r / t, u = 1.0 + 2.0 * s;
-      p = u * p;
-      double su = s / u;
-      r = (su * su) * r;
-    }
-  }
-  return p;
-}
-// d[n] diag, e[n] with e[0] ignored (e[i] couples i-1,i); z column-major n x n or null.
-// FAST: hypot in place of EISPACK's iterative pythag (the restart
-// eigenproblem of the thick-restart solver; Ritz values of the plain
-// Lanczos keep the reference's pythag)
-template <bool FAST = false>
-static int tql2(int n, double* d, double* e, double* z) {
-  if (n == 1) return 0;
-  for (int i = 1; i < n; i++) e[i - 1] = e[i];
-  e[n - 1] = 0.0;
-  double f = 0.0, tst1 = 0.0;
-  for (int l = 0; l < n; l++) {
-    int j = 0;
-    tst1 = std::max(tst1, fabs(d[l]) + fabs(e[l]));
-    int m = l;
-    for (; m < n; m++)
-      if (tst1 + fabs(e[m]) == tst1) break;
-    if (m != l) {
-      for (;;) {
-        if (j >= 30) return l + 1;
-        j++;
-        int l1 = l + 1, l2 = l1 + 1;
-        double g = d[l];
-        double p = (d[l1] - g) / (2.0 * e[l]);
-        double r = FAST ? hypot(p, 1.0) : pythag(p, 1.0);
-        double sr = p >= 0.0 ? fabs(r) : -fabs(r);
-        d[l] = e[l] / (p + sr);
-        d[l1] = e[l] * (p + sr);
-        double dl1 = d[l1];
-        double h = g - d[l];
-        for (int i = l2; i < n; i++) d[i] -= h;
-        f += h;
-        p = d[m];
-        double c = 1.0, c2 = c, c3 = c, el1 = e[l1], s = 0.0, s2 = 0.0;
-        for (int i = m - 1; i >= l; i--) {
-          c3 = c2;
-          c2 = c;
-          s2 = s;
-          g = c * e[i];
-          h = c * p;
-          r = FAST ? hypot(p, e[i]) : pythag(p, e[i]);
-          e[i + 1] = s * r;
-          s = e[i] / r;
-          c = p / r;
-          p = c * d[i] - s * g;
-          d[i + 1] = h + s * (c * g + s * d[i]);
-          if (z)
-            for (int k = 0; k < n; k++) {
-              h = z[k + (size_t)n * (i + 1)];
-              z[k + (size_t)n * (i + 1)] = s * z[k + (size_t)n * i] + c * h;
-              z[k + (size_t)n * i] = c * z[k + (size_t)n * i] - s * h;
-            }
-        }
-        p = -s * s2 * c3 * el1 * e[l] / dl1;
-        e[l] = s * p;
-        d[l] = c * p;
-        if (!(tst1 + fabs(e[l]) > tst1)) break;
-      }
-    }
-    d[l] += f;
-  }
-  for (int ii = 1; ii < n; ii++) {
-    int i = ii - 1, k = i;
-    double p = d[i];
-    for (int jj = ii; jj < n; jj++)
-      if (d[jj] < p) { k = jj; p = d[jj]; }
-    if (k != i) {
-      d[k] = d[i];
-      d[i] = p;
-      if (z)
-        for (int jj = 0; jj < n; jj++) std::swap(z[jj + (size_t)n * i], z[jj + (size_t)n * k]);
-    }
-  }
-  return 0;
-}
-
-static double lowest_ritz(const std::vector<double>& a, const std::vector<double>& b, int n) {
-  std::vector<double> d(a.begin(), a.begin() + n), e(n, 0.0);
-  for (int q = 1; q < n; q++) e[q] = b[q];
-  tql2(n, d.data(), e.data(), nullptr);
-  return d[0];
-}
-
-// ------------------------------------------ thick-restart Lanczos (ARPACK)
-// Cyclic Jacobi for a small real symmetric matrix (host): A (n x n, column-
-// major) -> ascending eigenvalues w, eigenvectors Z (column-major).
-static void jacobi_eigh(int n, std::vector<double> A, std::vector<double>& w, std::vector<double>& Z) {
-  Z.assign((size_t)n * n, 0.0);
-  for (int i = 0; i < n; i++) Z[i + (size_t)n * i] = 1.0;
-  auto a = [&](int i, int j) -> double& { return A[i + (size_t)n * j]; };
-  for (int sweep = 0; sweep < 100; sweep++) {
-    double off = 0.0, tot = 0.0;
-    for (int j = 0; j < n; j++)
-      for (int i = 0; i < n; i++) {
-        tot += a(i, j) * a(i, j);
-        if (i != j) off += a(i, j) * a(i, j);
-      }
-    if (off <= 1e-30 * tot || off == 0.0) break;
-    for (int p = 0; p < n - 1; p++)
-      for (int q = p + 1; q < n; q++) {
-        const double apq = a(p, q);
-        if (apq == 0.0) continue;
-        const double theta = (a(q, q) - a(p, p)) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-        for (int k = 0; k < n; k++) {  // A <- A J
-          const double akp = a(k, p), akq = a(k, q);
-          a(k, p) = c * akp - sn * akq;
-          a(k, q) = sn * akp + c * akq;
-        }
-        for (int k = 0; k < n; k++) {  // A <- J^T A
-          const double apk = a(p, k), aqk = a(q, k);
-          a(p, k) = c * apk - sn * aqk;
-          a(q, k) = sn * apk + c * aqk;
-        }
-        for (int k = 0; k < n; k++) {
-          const double zkp = Z[k + (size_t)n * p], zkq = Z[k + (size_t)n * q];
-          Z[k + (size_t)n * p] = c * zkp - sn * zkq;
-          Z[k + (size_t)n * q] = sn * zkp + c * zkq;
-        }
-      }
-  }
-  std::vector<int> idx(n);
-  for (int i = 0; i < n; i++) idx[i] = i;
-  std::sort(idx.begin(), idx.end(), [&](int x, int y) { return a(x, x) < a(y, y); });
-  std::vector<double> Zs((size_t)n * n);
-  w.assign(n, 0.0);
-  for (int k = 0; k < n; k++) {
-    w[k] = a(idx[k], idx[k]);
-    for (int i = 0; i < n; i++) Zs[i + (size_t)n * k] = Z[i + (size_t)n * idx[k]];
-  }
-  Z.swap(Zs);
-}
-
-// Householder reduction of a real symmetric matrix to tridiagonal form with
-// the transformation accumulated (EISPACK tred2 / Numerical Recipes §11.2):
-// A (n x n, column-major, A(i,j) = A[i + n*j]) is overwritten by Q with
-// Q^T A Q = tridiag(d, e), e[i] coupling i-1 and i (e[0] = 0).  With tql2
-// (same z convention) the projected matrix of a restart costs O(n^3) with a
-// small constant: the cyclic Jacobi took ~0.5 ms per 23 x 23 restart on the
-// host, most of a small sector's solve.
-static void tred2(int n, double* A, double* d, double* e) {
-#define TA(i, j) A[(i) + (size_t)n * (j)]
-  for (int i = n - 1; i > 0; i--) {
-    const int l = i - 1;
-    double h = 0.0, scale = 0.0;
-    if (l > 0) {
-      for (int k = 0; k <= l; k++) scale += fabs(TA(i, k));
-      if (scale == 0.0) {
-        e[i] = TA(i, l);
-      } else {
-        for (int k = 0; k <= l; k++) {
-          TA(i, k) /= scale;
-          h += TA(i, k) * TA(i, k);
-        }
-        double f = TA(i, l);
-        double g = f >= 0.0 ? -sqrt(h) : sqrt(h);
-        e[i] = scale * g;
-        h -= f * g;
-        TA(i, l) = f - g;
-        f = 0.0;
-        for (int j = 0; j <= l; j++) {
-          TA(j, i) = TA(i, j) / h;
-          g = 0.0;
-          for (int k = 0; k <= j; k++) g += TA(j, k) * TA(i, k);
-          for (int k = j + 1; k <= l; k++) g += TA(k, j) * TA(i, k);
-          e[j] = g / h;
-          f += e[j] * TA(i, j);
-        }
-        const double hh = f / (h + h);
-        for (int j = 0; j <= l; j++) {
-          f = TA(i, j);
-          e[j] = g = e[j] - hh * f;
-          for (int k = 0; k <= j; k++) TA(j, k) -= (f * e[k] + g * TA(i, k));
-        }
-      }
-    } else {
-      e[i] = TA(i, l);
-    }
-    d[i] = h;
-  }
-  d[0] = 0.0;
-  e[0] = 0.0;
-  for (int i = 0; i < n; i++) {
-    const int l = i - 1;
-    if (d[i] != 0.0) {
-      for (int j = 0; j <= l; j++) {
-        double g = 0.0;
-        for (int k = 0; k <= l; k++) g += TA(i, k) * TA(k, j);
-        for (int k = 0; k <= l; k++) TA(k, j) -= g * TA(k, i);
-      }
-    }
-    d[i] = TA(i, i);
-    TA(i, i) = 1.0;
-    for (int j = 0; j <= l; j++) TA(j, i) = TA(i, j) = 0.0;
-  }
-#undef TA
-}
-
-// Symmetric eigenproblem of the projected matrix: ascending w, eigenvectors
-// as the columns of Z (column-major).  tred2 + tql2; the cyclic Jacobi only if
-// the QL iteration does not converge.
-static void sym_eigh(int n, const std::vector<double>& A, std::vector<double>& w, std::vector<double>& Z) {
-  Z = A;
-  w.assign(n, 0.0);
-  std::vector<double> e(n, 0.0);
-  tred2(n, Z.data(), w.data(), e.data());
-  if (tql2<true>(n, w.data(), e.data(), Z.data()) != 0) jacobi_eigh(n, A, w, Z);
-}
+// (the host eigen-solvers and the restart / screen decisions: ed_hosteig.hpp)
 
 __global__ void k_hash_vec(double* v, int64_t n, uint64_t seed) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    uint64_t z = (uint64_t)(i + 1 + seed * 0x632BE59BD9B4E019ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
-    v[i] = (double)(z >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
+    v[i] = hash_vec_unit(i, seed);
   }
 }
 
@@ -2544,7 +2334,7 @@ struct Trlan {
   int* lof = nullptr;     // device: the current step's update was local-only
   double *Y = nullptr, *npart = nullptr, *alpha = nullptr, *beta = nullptr;
   double *npA = nullptr, *npB = nullptr;  // |w|^2 partials before / after the first CGS pass (DGKS)
-  double* hp = nullptr;          // pinned staging (trlan_pinned)
+  double* hp = nullptr;          // pinned staging (TrlStage)
   std::vector<void*> mine;
   std::vector<std::pair<int, hipGraphExec_t>> graphs;
   int nhv = 0;
@@ -2736,19 +2526,14 @@ struct Trlan {
   }
 };
 
-// Pinned host staging of the per-restart copies (alpha/beta down, the
-// projected eigenvectors up): pageable copies go through the runtime's
-// staging buffer, a CPU copy and an extra wait each, three per restart.  One
-// buffer per host thread, allocated on first use and kept (a farm worker
-// reuses it for every sector; freeing pinned memory can synchronise the
-// device under the other workers' streams).
-static constexpr int kPinnedDoubles = 2 * (64 + 8) + 64 * 64 + 16;
-static double* trlan_pinned() {
-  static thread_local double* buf = nullptr;
-  if (!buf && hipHostMalloc((void**)&buf, kPinnedDoubles * sizeof(double), hipHostMallocDefault) != hipSuccess)
-    buf = nullptr;
-  return buf;
-}
+// Pinned staging of one thick-restart solve (trlan_run's PinnedLease), offsets
+// in doubles: alpha/beta down, the projected eigenvectors up (pageable copies
+// go through the runtime's staging buffer, a CPU copy and an extra wait each,
+// three per restart).  The device alpha | beta blocks have the same spacing.
+struct TrlStage {
+  static constexpr int kAlpha = 0, kBeta = kTrlanMaxCols + 8, kZ = 2 * kBeta;  // Z: up to 64 x 64
+  static constexpr int kScalar = kZ + kTrlanMaxCols * kTrlanMaxCols + 8, kDoubles = kScalar + 8;
+};
 
 // blocks of the O(dim) Krylov sweeps
 // (1024 until round 4: 512 measured 13 % faster per large-sector solve,
@@ -2785,48 +2570,31 @@ static int trlan_core(Trlan<VC>& T, int k0, int nev, int maxit, double tol, cons
   else if (seed == 0) hipLaunchKernelGGL(k_default_start, dim3(grid_for(nd)), dim3(kBlock), 0, st, (double*)T.w, nd);
   else hipLaunchKernelGGL(k_hash_vec, dim3(grid_for(nd)), dim3(kBlock), 0, st, (double*)T.w, nd, seed);
   CK(T.orth(k0, T.w, -1));  // CGS2 against the locked columns; the norm -> beta[m]
-  double* const hp = T.hp;  // pinned: [0, 72) alpha, [72, 144) beta, [144, ...) Z, last: scalars
-  double* const hal = hp;
-  double* const hbe = hp + 72;
-  double* const hZ = hp + 144;
-  double* const hs = hp + kPinnedDoubles - 8;
+  double* const hal = T.hp + TrlStage::kAlpha;
+  double* const hbe = T.hp + TrlStage::kBeta;
+  double* const hZ = T.hp + TrlStage::kZ;
+  double* const hs = T.hp + TrlStage::kScalar;
   HIPCK(hipMemcpyAsync(hs, T.beta + m, sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCK(hipStreamSynchronize(st));
   const double b0 = hs[0];
   if (!(b0 > 0.0)) return fail(ED_ERR_ARG, "zero start vector");
   hipLaunchKernelGGL(k_scale_into<VC>, dim3(g), dim3(kBlock), 0, st, T.w, T.col(T.Vb, k0), T.beta + m, dim);
 
-  std::vector<double> Tm((size_t)ma * ma, 0.0), al(m), be(m);
-  auto tm = [&](int i, int j) -> double& { return Tm[i + (size_t)ma * j]; };
+  std::vector<double> Tm((size_t)ma * ma, 0.0);
   int jstart = k0, conv = 0;
   uint64_t rseed = seed * 7919 + 1;
   for (int it = 0; it < maxit; it++) {
     int j0 = jstart;
     for (;;) {  // expansion j0..m-1, restarted past an invariant subspace
       CK(T.sweep(j0));
-      if (T.beta == T.alpha + (hbe - hal)) {
-        HIPCK(hipMemcpyAsync(hal, T.alpha, ((hbe - hal) + m) * sizeof(double), hipMemcpyDeviceToHost, st));
-      } else {
-        HIPCK(hipMemcpyAsync(hal, T.alpha, m * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(hbe, T.beta, m * sizeof(double), hipMemcpyDeviceToHost, st));
-      }
+      // alpha | beta: one block on the device, laid out as the staging
+      HIPCK(hipMemcpyAsync(hal, T.alpha, (TrlStage::kBeta + m) * sizeof(double), hipMemcpyDeviceToHost, st));
       HIPCK(hipStreamSynchronize(st));
-      std::copy(hal, hal + m, al.begin());
-      std::copy(hbe, hbe + m, be.begin());
-      int jb = -1;
-      for (int j = j0; j < m; j++) {
-        const int l = j - k0;
-        tm(l, l) = al[j];
-        if (l + 1 < ma) tm(l, l + 1) = tm(l + 1, l) = be[j];
-        const double scale = fabs(al[j]) + (l > 0 ? fabs(tm(l - 1, l)) : 0.0) + 1e-300;
-        if (l + 1 < ma && be[j] < 1e-13 * scale) {
-          jb = j;
-          break;
-        }
-      }
+      const int jb = trl_fill(Tm.data(), ma, k0, j0, m, hal, hbe);
       if (jb < 0) break;
       // invariant subspace at jb: continue from a random direction orthogonal to V
-      tm(jb - k0, jb - k0 + 1) = tm(jb - k0 + 1, jb - k0) = 0.0;
+      const int lb = jb - k0;
+      Tm[lb + (size_t)ma * (lb + 1)] = Tm[(lb + 1) + (size_t)ma * lb] = 0.0;
       hipLaunchKernelGGL(k_hash_vec, dim3(grid_for(nd)), dim3(kBlock), 0, st, (double*)T.w, nd, rseed++);
       CK(T.orth(jb + 1, T.w, -1));
       hipLaunchKernelGGL(k_scale_into<VC>, dim3(g), dim3(kBlock), 0, st, T.w, T.col(T.Vb, jb + 1),
@@ -2835,18 +2603,11 @@ static int trlan_core(Trlan<VC>& T, int k0, int nev, int maxit, double tol, cons
       j0 = jb + 1;
       if (j0 >= m) break;
     }
-    const double beta = be[m - 1];
+    const double beta = hbe[m - 1];
     sym_eigh(ma, Tm, theta, Z);
-    // ARPACK-style test: |beta_m * Z(m-1,i)| <= tol * max(eps^(2/3), |theta_i|)
-    const double eps23 = 3.6e-11;
-    conv = 0;
-    for (int i = 0; i < nev; i++)
-      if (fabs(beta * Z[(ma - 1) + (size_t)ma * i]) <= tol * std::max(eps23, fabs(theta[i]))) conv++;
+    conv = trl_nconv(ma, nev, beta, theta.data(), Z.data(), tol);
     if (conv == nev || it == maxit - 1 || m == dim) break;
-    // thick restart: keep nkeep Ritz vectors + the residual direction
-    // (kept beyond nev: (ma - nev) / 2 — within 5 % of the best of 16
-    // restart-length variants on configs[3])
-    const int nkeep = std::max(nev, std::min(ma - 2, nev + (ma - nev) / 2));
+    const int nkeep = trl_nkeep(ma, nev);
     // (the previous restart's upload of hZ completed at this sweep's sync)
     std::copy(Z.begin(), Z.begin() + (size_t)ma * ma, hZ);
     HIPCK(hipMemcpyAsync(T.Y, hZ, (size_t)ma * ma * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2854,11 +2615,7 @@ static int trlan_core(Trlan<VC>& T, int k0, int nev, int maxit, double tol, cons
     hipLaunchKernelGGL(k_scale_into<VC>, dim3(g), dim3(kBlock), 0, st, T.w, T.col(T.Vb, k0 + nkeep),
                        T.beta + (m - 1), dim);
     HIPCK(hipGetLastError());
-    std::fill(Tm.begin(), Tm.end(), 0.0);
-    for (int i = 0; i < nkeep; i++) {
-      tm(i, i) = theta[i];
-      tm(i, nkeep) = tm(nkeep, i) = beta * Z[(ma - 1) + (size_t)ma * i];
-    }
+    trl_arrowhead(Tm.data(), ma, nkeep, beta, theta.data(), Z.data());
     jstart = k0 + nkeep;
   }
   *conv_out = conv;
@@ -2876,7 +2633,7 @@ static int trlan_core(Trlan<VC>& T, int k0, int nev, int maxit, double tol, cons
 // and the Krylov dimension is not capped by a restart.  Every kScreenChunk
 // steps the host forms the lowest Ritz value theta of the tridiagonal and
 // its residual bound |beta_k s_k| (first-row QL of the reversed matrix,
-// ed_tridiag_poles).  *below = 1: theta < cut — a certificate, since every
+// tridiag_poles).  *below = 1: theta < cut — a certificate, since every
 // Ritz value is a Rayleigh quotient and so >= the complement's lowest
 // eigenvalue (the thick-restart probe then finds its vector); 0: theta
 // converged to `tol` AND its whole residual interval [theta - r, theta + r]
@@ -2888,9 +2645,7 @@ static int trlan_core(Trlan<VC>& T, int k0, int nev, int maxit, double tol, cons
 // under the cut next to a well-converged theta just above it (r ~ tol|theta|
 // > theta - lambda_min) fails the interval test and the run goes on until
 // theta itself drops below the cut (tests/test_gpu_eigh.py adversarial case).
-constexpr int kScreenChunk = 10;
-constexpr int kScreenMaxSteps = 400;
-constexpr double kProbeMargin = 1e-11;
+// The rules themselves: screen_decide (ed_hosteig.hpp).
 // hint: column k0 holds the next Ritz vector of the main solve (round 0 of
 // the probe) — the start vector is then the hash vector plus that Ritz
 // vector at equal norm.  Where nothing was missed the complement's lowest
@@ -2930,7 +2685,8 @@ static int probe_screen(Trlan<VC>& T, int k0, int maxsteps, double tol, double c
   hipLaunchKernelGGL(k_scale_into<VC>, dim3(grid_for(dim)), dim3(kBlock), 0, st, T.w, T.col(T.Vb, ca),
                      T.beta + T.m, dim);
   HIPCK(hipGetLastError());
-  double* const hp = T.hp;  // pinned staging: alpha | beta of one chunk
+  double* const hal = T.hp + TrlStage::kAlpha;  // alpha | beta of one chunk
+  double* const hbe = T.hp + TrlStage::kBeta;
   std::vector<double> al, be;
   for (int k0s = 0; k0s < maxsteps; k0s += kScreenChunk) {
     const int k1 = std::min(maxsteps, k0s + kScreenChunk);
@@ -2948,31 +2704,14 @@ static int probe_screen(Trlan<VC>& T, int k0, int maxsteps, double tol, double c
       CK(T.orth(k0 + 2, T.w, k, T.col(T.Vb, prv), k > 0 ? 1 : 0, cur));
     }
     const int n = k1 - k0s;
-    HIPCK(hipMemcpyAsync(hp, pa + k0s, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(hp + 72, pb + k0s, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(hal, pa + k0s, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(hbe, pb + k0s, n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
-    al.insert(al.end(), hp, hp + n);
-    be.insert(be.end(), hp + 72, hp + 72 + n);
-    // lowest Ritz value and the last component of its vector: the reversed
-    // tridiagonal's first components
-    const int K = (int)al.size();
-    std::vector<double> ar(K), br(K, 0.0), E(K), z2(K), z1(K);
-    for (int i = 0; i < K; i++) ar[i] = al[K - 1 - i];
-    for (int i = 1; i < K; i++) br[i] = be[K - 1 - i];
-    if (ed_tridiag_poles(K, ar.data(), br.data(), E.data(), z2.data(), z1.data()) != ED_OK) return ED_OK;
-    const double theta = E[0], resid = fabs(be[K - 1] * z1[0]);
-    if (theta < cut) {
-      *below = 1;
-      return ED_OK;
-    }
-    // invariant Krylov space: theta is an exact eigenvalue of the complement
-    // restricted to it (the hash start vector reaches every eigenvector)
-    const bool invariant = be[K - 1] < 1e-13 * (fabs(theta) + 1e-300);
-    const bool converged = resid <= tol * std::max(3.6e-11, fabs(theta));
-    if (invariant || (converged && theta - resid > cut)) {
-      *below = 0;
-      return ED_OK;
-    }
+    al.insert(al.end(), hal, hal + n);
+    be.insert(be.end(), hbe, hbe + n);
+    const ScreenVerdict v = screen_decide(al, be, cut, tol);
+    if (v == kScreenNone || v == kScreenBelow) *below = v;
+    if (v != kScreenUndecided) return ED_OK;  // (QL failed: left undecided)
   }
   return ED_OK;
 }
@@ -2996,8 +2735,6 @@ static int trlan_run(ed_sector* s, int nev, int ncv, int maxit, double tol, cons
   T.st = s->stream;
   T.dim = s->dim;
   T.G = (int)std::min<int64_t>(grid_for(s->dim), s->dim > kTrlanBigDim ? 2 * kTrlanGridCap : kTrlanGridCap);
-  T.hp = trlan_pinned();
-  if (!T.hp) return fail(ED_ERR_OOM, "pinned host staging buffer");
   T.fused = !(s->opts & ED_OPT_TRLAN_UNFUSED);
   if (s->opts & ED_OPT_TRLAN_NOFOLD) T.kFinFoldG = 0;
   T.graphs_on = !(s->opts & ED_OPT_NO_GRAPH);
@@ -3007,12 +2744,12 @@ static int trlan_run(ed_sector* s, int nev, int ncv, int maxit, double tol, cons
   const int64_t dim = s->dim;
   const int m = (int)std::min<int64_t>(ncv, dim);
   if (nev < 1 || nev >= m) return fail(ED_ERR_ARG, "need 1 <= nev < min(ncv, dim)");
-  // deflated solves: nev locked columns + mp active ones, within the 64
-  // columns the coefficient buffers hold (h/coef/part/alpha/beta below)
-  constexpr int kProbeNcv = 20;
-  const int mp = (int)std::min<int64_t>(std::min(std::min(m, kProbeNcv), kTrlanMaxCols - nev), dim - nev);
-  const bool verify = !(s->opts & ED_OPT_EIGH_NO_VERIFY) && dim > (int64_t)nev + 2 && mp >= 3;
-  const int mcap = verify ? std::max(m, nev + mp) : m;
+  PinnedLease stage(TrlStage::kDoubles * sizeof(double), T.st);
+  T.hp = (double*)stage.p;
+  if (!T.hp) return fail(ED_ERR_OOM, "pinned host staging buffer");
+  // the degeneracy probe's deflated solves need nev + mp basis columns
+  const ScreenPlan may = screen_setup(m, nev, dim, s->opts, nev, 0.0, tol);
+  const int mp = may.mp, mcap = may.verify ? std::max(m, nev + mp) : m;
   T.mcap = mcap;
   const size_t vs = sizeof(V);
   CK(T.alloc((void**)&T.Vb, (size_t)mcap * dim * vs));
@@ -3025,10 +2762,9 @@ static int trlan_run(ed_sector* s, int nev, int ncv, int maxit, double tol, cons
   CK(T.alloc((void**)&T.npA, (size_t)T.G * sizeof(double)));
   CK(T.alloc((void**)&T.npB, (size_t)T.G * sizeof(double)));
   CK(T.alloc((void**)&T.lof, sizeof(int)));
-  // alpha | beta in one block laid out as the pinned staging (72 apart): one
-  // copy down per restart
-  CK(T.alloc((void**)&T.alpha, 2 * (kTrlanMaxCols + 8) * sizeof(double)));
-  T.beta = T.alpha + (kTrlanMaxCols + 8);
+  // alpha | beta in one block laid out as the staging: one copy down per restart
+  CK(T.alloc((void**)&T.alpha, 2 * TrlStage::kBeta * sizeof(double)));
+  T.beta = T.alpha + TrlStage::kBeta;
   CK(T.alloc((void**)&T.Y, (size_t)mcap * mcap * sizeof(double)));
   hipStream_t st = T.st;
   const int g = grid_for(dim);
@@ -3039,12 +2775,13 @@ static int trlan_run(ed_sector* s, int nev, int ncv, int maxit, double tol, cons
   // Ritz vectors -> Vb[0, nev): the result vectors live there from here on
   // (locked columns of the deflated solves); with the probe also the next
   // Ritz vector -> Vb[nev] (the screen's start hint)
-  std::copy(Z.begin(), Z.begin() + (size_t)m * m, T.hp + 144);
-  HIPCK(hipMemcpyAsync(T.Y, T.hp + 144, (size_t)m * m * sizeof(double), hipMemcpyHostToDevice, st));
-  const bool hint = verify && conv == nev && nev + 1 < m && !(s->opts & ED_OPT_EIGH_NOHINT);
-  CK(T.rotate(0, m, hint ? nev + 1 : nev, g));
+  double* const hZ = T.hp + TrlStage::kZ;
+  std::copy(Z.begin(), Z.begin() + (size_t)m * m, hZ);
+  HIPCK(hipMemcpyAsync(T.Y, hZ, (size_t)m * m * sizeof(double), hipMemcpyHostToDevice, st));
+  const ScreenPlan sp = screen_setup(m, nev, dim, s->opts, conv, theta[nev - 1], tol);
+  CK(T.rotate(0, m, sp.hint ? nev + 1 : nev, g));
   std::vector<double> ev(theta.begin(), theta.begin() + nev);
-  if (verify && conv == nev) {
+  if (sp.verify) {
     for (int round = 0; round < nev; round++) {
       // solve for the lowest eigenvalue on the complement of the nev vectors
       for (auto& gr : T.graphs) (void)hipGraphExecDestroy(gr.second);
@@ -3052,21 +2789,13 @@ static int trlan_run(ed_sector* s, int nev, int ncv, int maxit, double tol, cons
       T.m = nev + mp;
       std::vector<double> th2, Z2;
       int c2 = 0;
-      // the screen's "none" needs only a loose tolerance on top of its
-      // residual-interval test (Ritz values approach the lowest from above)
-      constexpr double kProbeTol = 1e-5;  // 1e-3 misses copies; 1e-4 and 1e-5 find them
-      const double tprobe = std::max(tol, kProbeTol);
-      // a copy missed within the margin below ev[nev-1] stays missed, so the
-      // margin sits under the 1e-10 Ritz-value bar (round 5: 1e-9, which let
-      // a pair 3e-10 below the top through; tests/golden/adversarial_probe.json)
-      const double cut = ev[nev - 1] - kProbeMargin * std::max(1.0, fabs(ev[nev - 1]));
+      const double cut = screen_cut(ev[nev - 1]);  // (a found copy moves ev[nev-1])
       if (!(s->opts & ED_OPT_EIGH_FULLPROBE)) {
         // cheap screen first: a plain Lanczos run on the complement decides
         // most sectors (no missed eigenvalue); the thick-restart probe below
         // runs only when it finds one or cannot decide
         int scr = -1;
-        CK(probe_screen(T, nev, (int)std::min<int64_t>(dim - nev, kScreenMaxSteps), tprobe, cut, 3000 + round,
-                        &scr, hint && round == 0));
+        CK(probe_screen(T, nev, sp.maxsteps, sp.tprobe, cut, 3000 + round, &scr, sp.hint && round == 0));
         if (scr == 0) break;
       }
       // the thick-restart probe at the full tolerance: its converged Ritz
@@ -3080,8 +2809,8 @@ static int trlan_run(ed_sector* s, int nev, int ncv, int maxit, double tol, cons
       // a missed eigenvalue: its Ritz vector -> w, then insert in order
       // (drop the current largest)
       const int ma2 = T.m - nev;
-      std::copy(Z2.begin(), Z2.begin() + ma2, T.hp + 144);
-      HIPCK(hipMemcpyAsync(T.Y, T.hp + 144, (size_t)ma2 * sizeof(double), hipMemcpyHostToDevice, st));
+      std::copy(Z2.begin(), Z2.begin() + ma2, hZ);
+      HIPCK(hipMemcpyAsync(T.Y, hZ, (size_t)ma2 * sizeof(double), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_rotate<VC>, dim3(std::min(g, 2048)), dim3(kBlock), (size_t)ma2 * sizeof(double), st,
                          T.col(T.Vb, nev), ma2, T.Y, ma2, 1, T.w, dim);
       HIPCK(hipGetLastError());
@@ -3121,32 +2850,10 @@ struct TbSec {
   int m = 0, it = 0, j0 = 0, conv = 0, nhv = 0;
   int state = 0;  // 0 main solve, 1 screen, 2 final rotation pending, 3 done, 4 fall back
   std::vector<double> Tm, theta, Z, ev, sal, sbe;
-  int maxsteps = 0, sk = 0;
-  double cut = 0.0, tprobe = 0.0;
-  bool hint = false;
+  ScreenPlan sp{};  // state 1
   TrlTask task{};
   int ny = 0;  // next launch's rotation: the first ny entries of Z (ld m)
 };
-
-static double host_default_start(int64_t r) {  // k_default_start's value
-  uint64_t z = (uint64_t)(r + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (double)(z >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
-}
-static char* tb_pinned(size_t n) {  // per host thread, grown on demand, kept
-  static thread_local char* buf = nullptr;
-  static thread_local size_t cap = 0;
-  if (n > cap) {
-    if (buf) (void)hipHostFree(buf);
-    buf = nullptr;
-    cap = 0;
-    if (hipHostMalloc((void**)&buf, n, hipHostMallocDefault) != hipSuccess) return nullptr;
-    cap = n;
-  }
-  return buf;
-}
 
 static bool tb_eligible(const ed_sector* s, int nev, int ncv) {
   const int m = (int)std::min<int64_t>(ncv, s->dim);
@@ -3159,64 +2866,45 @@ static bool tb_eligible(const ed_sector* s, int nev, int ncv) {
 
 // One sector's host step after a cycle of the batch (ed_trlbatch.hpp) or of
 // the lockstep multi-sector solve (ed_trlmulti.hpp), on its mailbox ml
-// (alpha [0, 32) | beta [32, 64) | scalar [64]): trlan_core's projected
-// eigenproblem, ARPACK convergence test and thick restart, then
-// probe_screen's decisions; sets the sector's next task (b.task, b.ny).
+// (alpha [0, 32) | beta [32, 64) | scalar [64]): trlan_core's cycle with
+// k0 = 0 and then probe_screen's, as a state machine over the same decisions
+// (ed_hosteig.hpp); sets the sector's next task (b.task, b.ny).
 static void tb_advance(TbSec& b, const double* ml, int nev, int maxit, double tol) {
   TrlTask& t = b.task;
-  const int m = b.m, ma = m;
+  const int m = b.m;
+  const double *al = ml, *be = ml + 32;
   b.ny = 0;
-  auto tm = [&](int i, int j) -> double& { return b.Tm[i + (size_t)ma * j]; };
-  if (b.state == 0) {  // a main sweep [j0, m) ran (trlan_core)
+  if (b.state == 0) {  // a main sweep [j0, m) ran
     if (t.op == kTbStart && !(ml[64] > 0.0)) {
       b.state = 4;
       return;
     }
     b.nhv += m - b.j0;
-    int jb = -1;
-    for (int j = b.j0; j < m; j++) {
-      tm(j, j) = ml[j];
-      if (j + 1 < ma) tm(j, j + 1) = tm(j + 1, j) = ml[32 + j];
-      const double scale = fabs(ml[j]) + (j > 0 ? fabs(tm(j - 1, j)) : 0.0) + 1e-300;
-      if (j + 1 < ma && ml[32 + j] < 1e-13 * scale) {
-        jb = j;
-        break;
-      }
-    }
-    if (jb >= 0) {  // invariant subspace: trlan_run continues from a random direction
-      b.state = 4;
+    if (trl_fill(b.Tm.data(), m, 0, b.j0, m, al, be) >= 0) {
+      b.state = 4;  // invariant subspace: trlan_run continues from a random direction
       return;
     }
-    const double beta = ml[32 + m - 1];
-    sym_eigh(ma, b.Tm, b.theta, b.Z);
-    const double eps23 = 3.6e-11;
-    b.conv = 0;
-    for (int i = 0; i < nev; i++)
-      if (fabs(beta * b.Z[(ma - 1) + (size_t)ma * i]) <= tol * std::max(eps23, fabs(b.theta[i]))) b.conv++;
+    const double beta = be[m - 1];
+    sym_eigh(m, b.Tm, b.theta, b.Z);
+    b.conv = trl_nconv(m, nev, beta, b.theta.data(), b.Z.data(), tol);
     if (b.conv == nev || b.it == maxit - 1 || m == b.dim) {
       b.ev.assign(b.theta.begin(), b.theta.begin() + nev);
-      const int mp = (int)std::min<int64_t>(std::min(std::min(m, 20), kTrlanMaxCols - nev), b.dim - nev);
-      const bool verify = !(b.s->opts & ED_OPT_EIGH_NO_VERIFY) && mp >= 3 && b.conv == nev;
-      if (verify && (b.s->opts & ED_OPT_EIGH_FULLPROBE)) {
+      const ScreenPlan sp = screen_setup(m, nev, b.dim, b.s->opts, b.conv, b.ev[nev - 1], tol);
+      if (sp.verify && (b.s->opts & ED_OPT_EIGH_FULLPROBE)) {
         b.state = 4;
         return;
       }
-      b.hint = verify && nev + 1 < m && !(b.s->opts & ED_OPT_EIGH_NOHINT);
-      const int nrot = b.hint ? nev + 1 : nev;
       t.op = kTbScreen;
-      t.ldy = ma;
-      t.nrot = nrot;
-      b.ny = ma * nrot;
+      t.ldy = m;
+      t.nrot = sp.hint ? nev + 1 : nev;
+      b.ny = m * t.nrot;
       t.k0s = 0;
-      if (verify) {
+      if (sp.verify) {
         b.state = 1;
-        b.maxsteps = (int)std::min<int64_t>(b.dim - nev, kScreenMaxSteps);
-        b.cut = b.ev[nev - 1] - kProbeMargin * std::max(1.0, fabs(b.ev[nev - 1]));
-        b.tprobe = std::max(tol, 1e-5);
-        t.k1 = std::min(b.maxsteps, kScreenChunk);
-        t.hint = b.hint ? 1 : 0;
+        b.sp = sp;
+        t.k1 = std::min(sp.maxsteps, kScreenChunk);
+        t.hint = sp.hint ? 1 : 0;
         t.seed = 3000;
-        b.sk = 0;
         b.sal.clear();
         b.sbe.clear();
       } else {
@@ -3225,17 +2913,12 @@ static void tb_advance(TbSec& b, const double* ml, int nev, int maxit, double to
       }
       return;
     }
-    // thick restart (trlan_core)
-    const int nkeep = std::max(nev, std::min(ma - 2, nev + (ma - nev) / 2));
+    const int nkeep = trl_nkeep(m, nev);
     t.op = kTbRestart;
-    t.ldy = ma;
+    t.ldy = m;
     t.nrot = nkeep;
-    b.ny = ma * nkeep;
-    std::fill(b.Tm.begin(), b.Tm.end(), 0.0);
-    for (int i = 0; i < nkeep; i++) {
-      tm(i, i) = b.theta[i];
-      tm(i, nkeep) = tm(nkeep, i) = beta * b.Z[(ma - 1) + (size_t)ma * i];
-    }
+    b.ny = m * nkeep;
+    trl_arrowhead(b.Tm.data(), m, nkeep, beta, b.theta.data(), b.Z.data());
     b.j0 = nkeep;
     b.it++;
     return;
@@ -3244,35 +2927,18 @@ static void tb_advance(TbSec& b, const double* ml, int nev, int maxit, double to
     b.state = 3;
     return;
   }
-  // a screen chunk [k0s, k1) ran (probe_screen)
+  // a screen chunk [k0s, k1) ran
   const int nst = t.k1 - t.k0s;
   b.nhv += nst;
-  for (int q = 0; q < nst; q++) {
-    b.sal.push_back(ml[q]);
-    b.sbe.push_back(ml[32 + q]);
-  }
+  b.sal.insert(b.sal.end(), al, al + nst);
+  b.sbe.insert(b.sbe.end(), be, be + nst);
   t.nrot = 0;
-  const int K = (int)b.sal.size();
-  std::vector<double> ar(K), br(K, 0.0), E(K), z2(K), z1(K);
-  for (int i = 0; i < K; i++) ar[i] = b.sal[K - 1 - i];
-  for (int i = 1; i < K; i++) br[i] = b.sbe[K - 1 - i];
-  int dec = -1;
-  if (ed_tridiag_poles(K, ar.data(), br.data(), E.data(), z2.data(), z1.data()) == ED_OK) {
-    const double theta = E[0], resid = fabs(b.sbe[K - 1] * z1[0]);
-    if (theta < b.cut) dec = 1;
-    else {
-      const bool invariant = b.sbe[K - 1] < 1e-13 * (fabs(theta) + 1e-300);
-      const bool converged = resid <= b.tprobe * std::max(3.6e-11, fabs(theta));
-      if (invariant || (converged && theta - resid > b.cut)) dec = 0;
-    }
-  } else {
-    dec = 2;
-  }
-  if (dec == 0) b.state = 3;
-  else if (dec > 0 || t.k1 >= b.maxsteps) b.state = 4;
+  const ScreenVerdict v = screen_decide(b.sal, b.sbe, b.sp.cut, b.sp.tprobe);
+  if (v == kScreenNone) b.state = 3;
+  else if (v != kScreenUndecided || t.k1 >= b.sp.maxsteps) b.state = 4;
   else {
     t.k0s = t.k1;
-    t.k1 = std::min(b.maxsteps, t.k0s + kScreenChunk);
+    t.k1 = std::min(b.sp.maxsteps, t.k0s + kScreenChunk);
   }
 }
 
@@ -3336,6 +3002,27 @@ struct TbPool {
 };
 static constexpr int kTbHostThreads = 3;  // helpers beside the calling thread
 
+// Results of a batch / lockstep solve (S[k]: the call's sector idx[k], vectors
+// in task.Vb); unfinished sectors go to `fallback`, re-solved by the caller.
+static int tb_scatter(const std::vector<TbSec>& S, const std::vector<int>& idx, int nev, double* evals,
+                      void* const* evecs, int32_t* nconv, int32_t* nhv, hipStream_t st, std::vector<int>& fallback) {
+  for (size_t k = 0; k < S.size(); k++) {
+    const TbSec& b = S[k];
+    const int i = idx[k];
+    if (nhv) nhv[i] = b.nhv;
+    if (b.state != 3) {
+      fallback.push_back(i);
+      continue;
+    }
+    for (int e = 0; e < nev; e++) evals[(size_t)i * nev + e] = b.ev[e];
+    if (evecs && evecs[i])
+      HIPCK(hipMemcpyAsync(evecs[i], b.task.Vb, (size_t)nev * b.dim * sizeof(double), hipMemcpyDefault, st));
+    if (nconv) nconv[i] = b.conv;
+  }
+  HIPCK(hipStreamSynchronize(st));
+  return ED_OK;
+}
+
 static int tb_run(ed_sector* const* secs, const std::vector<int>& which, int nev, int ncv, const int32_t* maxits,
                   double tol, const double* const* v0, double* evals, void* const* evecs, int32_t* nconv,
                   int32_t* nhv, hipStream_t st, std::vector<int>& fallback) {
@@ -3355,9 +3042,9 @@ static int tb_run(ed_sector* const* secs, const std::vector<int>& which, int nev
   }
   const int ns = (int)S.size();
   if (ns == 0) return ED_OK;
-  // device: per sector Vb (mcap columns) | w | alpha, beta (72 each) | pa, pb
-  // | coef | Y; the ws of all sectors contiguous (one start-vector upload),
-  // the mailboxes contiguous (one copy down per launch)
+  // device: per sector Vb (mcap columns) | alpha, beta (72 each) | pa, pb
+  // | coef | Y, each on a 16-byte boundary; the ws of all sectors contiguous
+  // (one start-vector upload), the mailboxes too (one copy down per launch)
   size_t nw = 0, per = 0;
   std::vector<size_t> off(ns), woff(ns);
   for (int k = 0; k < ns; k++) {
@@ -3365,17 +3052,15 @@ static int tb_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     woff[k] = nw;
     nw += (size_t)S[k].dim;
     off[k] = per;
-    per += (size_t)mcap * S[k].dim + 2 * 72 + 2 * kTbScreenLen + 2 * kTrlanMaxCols + kTbMaxCols * kTbMaxCols;
+    per += even((size_t)mcap * S[k].dim) + 2 * TrlStage::kBeta + 2 * kTbScreenLen + 2 * kTrlanMaxCols +
+           kTbMaxCols * kTbMaxCols;
   }
   const size_t nmail = (size_t)ns * kTbMail;
   const size_t ytot = (size_t)ns * kTbMaxCols * kTbMaxCols;  // rotations of one launch, packed
   const size_t bytes = (per + nw + nmail + ytot) * sizeof(double) + (size_t)ns * sizeof(TrlTask);
   char* dbase = nullptr;
   HIPCK(hipMallocAsync((void**)&dbase, bytes, st));
-  struct Free {
-    char* p; hipStream_t s;
-    ~Free() { (void)hipFreeAsync(p, s); }
-  } free_guard{dbase, st};
+  DevFree free_guard{dbase, st};
   double* const dsec = (double*)dbase;
   double* const dw = dsec + per;
   double* const dmail = dw + nw;
@@ -3383,7 +3068,8 @@ static int tb_run(ed_sector* const* secs, const std::vector<int>& which, int nev
   // pinned: start vectors | mailboxes | tasks + rotations of one launch
   // (the device mirrors the last part: [tasks | rotations packed])
   const size_t hbytes = (nw + nmail + ytot) * sizeof(double) + (size_t)ns * sizeof(TrlTask);
-  char* hp = tb_pinned(hbytes);
+  PinnedLease stage(hbytes, st);
+  char* const hp = (char*)stage.p;
   if (!hp) return fail(ED_ERR_OOM, "pinned staging (batch eigh)");
   double* const hv0 = (double*)hp;
   double* const hmail = hv0 + nw;
@@ -3402,10 +3088,10 @@ static int tb_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     t.vals = (const double*)s->d_vals;
     t.dim = b.dim;
     t.Vb = p;
-    p += (size_t)mcap * b.dim;
+    p += even((size_t)mcap * b.dim);
     t.alpha = p;
-    t.beta = p + 72;
-    p += 144;
+    t.beta = p + TrlStage::kBeta;
+    p += 2 * TrlStage::kBeta;
     t.pa = p;
     t.pb = p + kTbScreenLen;
     p += 2 * kTbScreenLen;
@@ -3422,7 +3108,7 @@ static int tb_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     const int i = idx[k];
     if (v0 && v0[i]) memcpy(hv0 + woff[k], v0[i], b.dim * sizeof(double));
     else
-      for (int64_t r = 0; r < b.dim; r++) hv0[woff[k] + r] = host_default_start(r);
+      for (int64_t r = 0; r < b.dim; r++) hv0[woff[k] + r] = splitmix_unit((uint64_t)(r + 1));
   }
   HIPCK(hipMemcpyAsync(dw, hv0, nw * sizeof(double), hipMemcpyHostToDevice, st));
   static std::once_flag lds_once;
@@ -3479,23 +3165,7 @@ static int tb_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     HIPCK(hipStreamSynchronize(st));
     pool.run((int)act.size(), process);
   }
-  // results; fall-backs re-solved by the caller
-  for (int k = 0; k < ns; k++) {
-    TbSec& b = S[k];
-    const int i = idx[k];
-    if (b.state != 3) {
-      fallback.push_back(i);
-      if (nhv) nhv[i] = b.nhv;
-      continue;
-    }
-    for (int e = 0; e < nev; e++) evals[(size_t)i * nev + e] = b.ev[e];
-    if (evecs && evecs[i])
-      HIPCK(hipMemcpyAsync(evecs[i], b.task.Vb, (size_t)nev * b.dim * sizeof(double), hipMemcpyDefault, st));
-    if (nconv) nconv[i] = b.conv;
-    if (nhv) nhv[i] = b.nhv;
-  }
-  HIPCK(hipStreamSynchronize(st));
-  return ED_OK;
+  return tb_scatter(S, idx, nev, evals, evecs, nconv, nhv, st, fallback);
 }
 
 // ------------------------------------- lockstep multi-sector eigh
@@ -3538,9 +3208,8 @@ static int tm_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     const int mcap = std::max(b.m, nev + 2);
     off[k] = per;
     // (every sub-array starts on a 16-byte boundary: the double2 ones need it)
-    per += (size_t)mcap * b.dim + 2 + (size_t)b.dim + 2 + 4 * (size_t)kTrlanMaxCols * G +
-           (3 * (size_t)G + 1) / 2 * 2 + 4 * kTrlanMaxCols + 2 + 144 + 2 * kTbScreenLen;
-    per = (per + 1) & ~(size_t)1;
+    per += even((size_t)mcap * b.dim) + even(b.dim) + 4 * (size_t)kTrlanMaxCols * G + even(3 * (size_t)G) +
+           4 * kTrlanMaxCols + 2 + 2 * TrlStage::kBeta + 2 * kTbScreenLen;
   }
   const size_t nmail = (size_t)ns * kTbMail;
   const size_t ytot = (size_t)ns * kTbMaxCols * kTbMaxCols;
@@ -3548,10 +3217,7 @@ static int tm_run(ed_sector* const* secs, const std::vector<int>& which, int nev
   const size_t bytes = (per + nmail + ytot) * sizeof(double) + (size_t)ns * sizeof(TmSec) + ctab;
   char* dbase = nullptr;
   HIPCK(hipMallocAsync((void**)&dbase, bytes, st));
-  struct Free {
-    char* p; hipStream_t s;
-    ~Free() { (void)hipFreeAsync(p, s); }
-  } free_guard{dbase, st};
+  DevFree free_guard{dbase, st};
   double* const dsec = (double*)dbase;
   double* const dmail = dsec + per;
   TmSec* const dtab = (TmSec*)(dmail + nmail);
@@ -3559,7 +3225,8 @@ static int tm_run(ed_sector* const* secs, const std::vector<int>& which, int nev
   // pinned: start column / mailboxes | cycle table
   const int64_t maxdim = [&] { int64_t d = 0; for (auto& b : S) d = std::max(d, b.dim); return d; }();
   const size_t hbytes = std::max<size_t>(maxdim, nmail) * sizeof(double) + ctab + ytot * sizeof(double);
-  char* hp = tb_pinned(hbytes);
+  PinnedLease stage(hbytes, st);
+  char* const hp = (char*)stage.p;
   if (!hp) return fail(ED_ERR_OOM, "pinned staging (multi-sector eigh)");
   double* const hmail = (double*)hp;
   char* const hcyc = hp + std::max<size_t>(maxdim, nmail) * sizeof(double);
@@ -3576,8 +3243,8 @@ static int tm_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     t.dim = b.dim;
     // (columns at stride dim, as the sweeps index them; each sub-array starts
     // on a 16-byte boundary)
-    auto even = [](size_t q) { return (q + 1) & ~(size_t)1; };
     t.Vb = p;
+    b.task.Vb = p;  // (tb_scatter)
     p += even((size_t)mcap * b.dim);
     t.w = p;
     p += even(b.dim);
@@ -3588,17 +3255,16 @@ static int tm_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     t.npA = p;
     t.npB = p + t.G;
     t.npart = p + 2 * t.G;
-    p += (3 * (size_t)t.G + 1) / 2 * 2;
+    p += even(3 * (size_t)t.G);
     t.h = (double2*)p;
     t.coef = (double2*)(p + 2 * kTrlanMaxCols);
     p += 4 * kTrlanMaxCols;
     t.lof = (int*)p;
     p += 2;
     t.alpha = p;
-    t.beta = p + 72;
-    p += 144;
-    t.pa = p;
-    t.pb = p + kTbScreenLen;
+    t.beta = p + TrlStage::kBeta;
+    t.pa = p + 2 * TrlStage::kBeta;
+    t.pb = t.pa + kTbScreenLen;
     t.mail = dmail + (size_t)k * kTbMail;
     b.task.m = b.m;
     b.task.nev = nev;
@@ -3609,7 +3275,7 @@ static int tm_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     const int i = which[k];
     double n2 = 0.0;
     for (int64_t r = 0; r < b.dim; r++) {
-      h0[r] = (v0 && v0[i]) ? v0[i][r] : host_default_start(r);
+      h0[r] = (v0 && v0[i]) ? v0[i][r] : splitmix_unit((uint64_t)(r + 1));
       n2 += h0[r] * h0[r];
     }
     if (!(n2 > 0.0)) {
@@ -3706,22 +3372,7 @@ static int tm_run(ed_sector* const* secs, const std::vector<int>& which, int nev
     HIPCK(hipStreamSynchronize(st));
     pool.run(na, process);
   }
-  for (int k = 0; k < ns; k++) {
-    TbSec& b = S[k];
-    const int i = which[k];
-    if (b.state != 3) {
-      fallback.push_back(i);
-      if (nhv) nhv[i] = b.nhv;
-      continue;
-    }
-    for (int e = 0; e < nev; e++) evals[(size_t)i * nev + e] = b.ev[e];
-    if (evecs && evecs[i])
-      HIPCK(hipMemcpyAsync(evecs[i], hs[k].Vb, (size_t)nev * b.dim * sizeof(double), hipMemcpyDefault, st));
-    if (nconv) nconv[i] = b.conv;
-    if (nhv) nhv[i] = b.nhv;
-  }
-  HIPCK(hipStreamSynchronize(st));
-  return ED_OK;
+  return tb_scatter(S, which, nev, evals, evecs, nconv, nhv, st, fallback);
 }
 
 template <bool HC, bool VC>
@@ -4355,88 +4006,11 @@ int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t o
 // ED_GF_NORMAL.f90:612-618).  The EISPACK implicit-QL iteration with the
 // rotations applied to the first row of Z only (Z starts as the identity, so
 // that row starts as e_1): O(n^2) instead of the O(n^3) full eigenvector
-// accumulation; same pythag, shifts and convergence test as tql2.
-static double ql_pythag(double a, double b) {
-  double p = std::max(fabs(a), fabs(b));
-  if (p == 0.0) return p;
-  double r = std::min(fabs(a), fabs(b)) / p;
-  r = r * r;
-  for (;;) {
-    const double t = 4.0 + r;
-    if (t == 4.0) break;
-    const double q = r / t, u = 1.0 + 2.0 * q;
-    p = u * p;
-    const double qu = q / u;
-    r = (qu * qu) * r;
-  }
-  return p;
-}
-
+// accumulation; same pythag, shifts and convergence test as tql2
+// (ql_implicit's first-row sink, ed_hosteig.hpp).
 int ed_tridiag_poles(int32_t n, const double* alfa, const double* beta, double* E, double* z2, double* z1) {
   if (n < 1 || !alfa || !beta || !E || !z2) return fail(ED_ERR_ARG, "bad args");
-  std::vector<double> e(n, 0.0), z(n, 0.0);
-  for (int i = 0; i < n; i++) E[i] = alfa[i];
-  for (int i = 0; i + 1 < n; i++) e[i] = beta[i + 1];  // e[i] = T(i, i+1); e[n-1] = 0
-  z[0] = 1.0;
-  double f = 0.0, tst1 = 0.0;
-  for (int l = 0; l < n; l++) {
-    tst1 = std::max(tst1, fabs(E[l]) + fabs(e[l]));
-    int m = l;
-    while (m < n && tst1 + fabs(e[m]) != tst1) m++;
-    if (m >= n) m = n - 1;  // e[n-1] == 0 stops the scan at n-1
-    if (m != l) {
-      for (int it = 0;; it++) {
-        if (it >= 30) return fail(ED_ERR_NOCONV, "tridiagonal QL: no convergence");
-        const double g0 = E[l];
-        double p = (E[l + 1] - g0) / (2.0 * e[l]);
-        double r = ql_pythag(p, 1.0);
-        const double sr = p >= 0.0 ? fabs(r) : -fabs(r);
-        E[l] = e[l] / (p + sr);
-        E[l + 1] = e[l] * (p + sr);
-        const double dl1 = E[l + 1];
-        double h = g0 - E[l];
-        for (int i = l + 2; i < n; i++) E[i] -= h;
-        f += h;
-        p = E[m];
-        double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
-        const double el1 = e[l + 1];
-        for (int i = m - 1; i >= l; i--) {
-          c3 = c2;
-          c2 = c;
-          s2 = s;
-          const double g = c * e[i];
-          h = c * p;
-          r = ql_pythag(p, e[i]);
-          e[i + 1] = s * r;
-          s = e[i] / r;
-          c = p / r;
-          p = c * E[i] - s * g;
-          E[i + 1] = h + s * (c * g + s * E[i]);
-          const double zh = z[i + 1];  // first row of Z only
-          z[i + 1] = s * z[i] + c * zh;
-          z[i] = c * z[i] - s * zh;
-        }
-        p = -s * s2 * c3 * el1 * e[l] / dl1;
-        e[l] = s * p;
-        E[l] = c * p;
-        if (!(tst1 + fabs(e[l]) > tst1)) break;
-      }
-    }
-    E[l] += f;
-  }
-  // ascending order (selection sort, as tql2)
-  for (int i = 0; i + 1 < n; i++) {
-    int k = i;
-    for (int j = i + 1; j < n; j++)
-      if (E[j] < E[k]) k = j;
-    if (k != i) {
-      std::swap(E[i], E[k]);
-      std::swap(z[i], z[k]);
-    }
-  }
-  for (int i = 0; i < n; i++) z2[i] = z[i] * z[i];
-  if (z1)
-    for (int i = 0; i < n; i++) z1[i] = z[i];
+  if (tridiag_poles(n, alfa, beta, E, z2, z1) != 0) return fail(ED_ERR_NOCONV, "tridiagonal QL: no convergence");
   return ED_OK;
 }
 

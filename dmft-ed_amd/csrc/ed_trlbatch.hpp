@@ -19,6 +19,7 @@
 // orth_solo_body (CGS pass 1, local-only or full pass 2, DGKS pass 3,
 // alpha/beta, V_{j+1} = w / beta).
 #pragma once
+#include "ed_hosteig.hpp"
 #include "ed_trlan.hpp"
 
 namespace edg {
@@ -65,14 +66,6 @@ struct TrlTask {
   int locupd;       // local-only CGS update allowed (kCgsLocTol)
   uint64_t seed;    // screen start: hash vector seed (k_hash_vec)
 };
-
-__device__ __forceinline__ double tb_hash(int64_t i, uint64_t seed) {  // k_hash_vec's value
-  uint64_t z = (uint64_t)(i + 1 + seed * 0x632BE59BD9B4E019ull) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (double)(z >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
-}
 
 // w = H v (v staged in LDS vl, the slice pointers in LDS ssp); shifted:
 // w = (H - sg) v - bp vprev.  Row sums in slot order, diagonal first
@@ -256,7 +249,7 @@ __global__ void __launch_bounds__(kTbBlock) k_trl_batch(const TrlTask* __restric
   if (a.k0s == 0 && a.k1 > 0) {
     const double amix = sqrt((double)dim / 3.0);
     for (int64_t i = t; i < dim; i += kTbBlock) {
-      double h = tb_hash(i, a.seed);
+      double h = hash_vec_unit(i, a.seed);
       if (a.hint) h = h + amix * col(ca)[i];
       a.w[i] = h;
       col(cb)[i] = 0.0;  // v_{-1} = 0

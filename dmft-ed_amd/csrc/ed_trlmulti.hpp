@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(kBlock) k_tm_hxv(const TmSec* __restrict__ sec
     const double* hv = s.Vb + (int64_t)c.nev * dim;
     double* vcb = s.Vb + (int64_t)(c.nev + 1) * dim;
     for (int64_t i = (int64_t)bx * kBlock + threadIdx.x; i < dim; i += (int64_t)s.Gh * kBlock) {
-      double h = tb_hash(i, c.seed);
+      double h = hash_vec_unit(i, c.seed);
       if (c.hint) h = h + amix * hv[i];
       s.w[i] = h;
       vcb[i] = 0.0;
