@@ -31,6 +31,7 @@
 #include "ed_tables.hpp"
 #include "ed_host.hpp"
 #include "ed_hosteig.hpp"
+#include "ed_obs.hpp"
 
 using namespace edg;
 
@@ -3996,6 +3997,105 @@ int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t o
                        src->d_map, src->dim, idx, op, level, coef_re, coef_im,
                        (const double*)src_vec, (double*)dst_vec);
   HIPCK(hipGetLastError());
+  return ED_OK;
+}
+
+// ------------------------------------------------ observables of a kept state
+// (ed_obs.hpp).  Both calls make one grid-strided pass over (d_map, vec) on a
+// grid of at most kObsMaxGrid blocks, then one finishing launch that sums
+// every row of block partials in fixed order; the few results come back
+// through a pinned block.  Nothing is kept in the sector object.
+static constexpr int kObsMaxGrid = 1024;
+
+// observables_impurity's diagonal loop (ED_OBSERVABLES.f90:127-158) and the
+// density-density / Hartree sums of local_energy_impurity (:797-943) are
+// linear in these moments.
+int ed_sector_nn_moments(const ed_sector* s, int32_t vtype, const void* vec_dev, int32_t nlev,
+                         const int32_t* levels, double* out, void* stream) {
+  if (!s || !vec_dev || !levels || !out) return fail(ED_ERR_ARG, "null");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  static_assert(kObsMaxLev == 6, "launch_nn_moments instantiates 1..6 levels");
+  if (nlev < 1 || nlev > kObsMaxLev) return fail(ED_ERR_ARG, "nlev must be 1..2*ED_MAX_NORB");
+  ObsLevels L{};
+  for (int p = 0; p < nlev; p++) {
+    if (levels[p] < 0 || levels[p] >= 2 * s->Mh.ns) return fail(ED_ERR_ARG, "level outside the 2*Ns Fock levels");
+    L.lev[p] = levels[p];
+  }
+  CK(whole_only(s));
+  HIPCK(hipSetDevice(s->device));
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  const int nm = nlev * (nlev + 1) / 2 + 1;
+  const int g = std::min(grid_for(s->dim), kObsMaxGrid);
+  double* d = nullptr;
+  HIPCK(hipMallocAsync((void**)&d, ((size_t)nm * g + nm) * sizeof(double), st));
+  DevFree fr{d, st};
+  PinnedLease pin((size_t)nm * sizeof(double), st);
+  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
+  if (vtype) launch_nn_moments<true>(nlev, g, st, s->d_map, vec_dev, s->dim, L, d);
+  else launch_nn_moments<false>(nlev, g, st, s->d_map, vec_dev, s->dim, L, d);
+  HIPCK(hipGetLastError());
+  hipLaunchKernelGGL(k_obs_finish, dim3(nm), dim3(kBlock), 0, st, d, g, d + (size_t)nm * g);
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(pin.p, d + (size_t)nm * g, (size_t)nm * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  memcpy(out, pin.p, (size_t)nm * sizeof(double));
+  return ED_OK;
+}
+
+// The off-diagonal sums of observables_impurity (ED_OBSERVABLES.f90:556-581,
+// :631-654; magX/magY/phisc expanded, :166-337) and local_energy_impurity
+// (:802-846 hopping, :882-927 spin exchange and pair hopping) as expectation
+// values of operator strings.  Every string is compiled (and rejected if it
+// leaves the sector) before anything is launched.
+int ed_sector_expect(const ed_sector* s, int32_t vtype, const void* vec_dev, int32_t nterm, const int32_t* nops,
+                     const int32_t* levels, const int32_t* ops, double* out, void* stream) {
+  if (!s || !vec_dev || !nops || !levels || !ops || !out) return fail(ED_ERR_ARG, "null");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (nterm < 1) return fail(ED_ERR_ARG, "nterm must be positive");
+  CK(whole_only(s));
+  const ObsSector os{s->Mh.ns, s->Mh.mode, s->Mh.jz, s->Mh.lz2};
+  const int ntp = (nterm + kObsTile - 1) / kObsTile * kObsTile;  // padded with null terms
+  std::vector<ObsTerm> terms((size_t)ntp, obs_null_term());
+  for (int t = 0, o = 0; t < nterm; t++) {
+    if (nops[t] < 1 || nops[t] > kObsMaxOps)
+      return fail(ED_ERR_ARG, "term " + std::to_string(t) + ": 1..4 operators per string");
+    if (obs_compile(os, nops[t], levels + o, ops + o, &terms[t]) != ED_OK)
+      return fail(ED_ERR_ARG, "term " + std::to_string(t) + ": bad level/op, or the string leaves the sector");
+    o += nops[t];
+  }
+  HIPCK(hipSetDevice(s->device));
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  const int g = std::min(grid_for(s->dim), kObsMaxGrid);
+  const int w = vtype ? 2 : 1;  // partial rows per term
+  const size_t nval = (size_t)w * ntp;
+  double* d = nullptr;
+  HIPCK(hipMallocAsync((void**)&d, (nval * g + nval) * sizeof(double), st));
+  DevFree fr{d, st};
+  PinnedLease pin(nval * sizeof(double), st);
+  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
+  const DevIndex idx{s->d_off, s->d_rank, s->T.ns, s->T.nst - 1};
+  for (int t0 = 0; t0 < ntp; t0 += kObsMaxTerms) {
+    const int n = std::min(kObsMaxTerms, ntp - t0);
+    ObsTermList TL;
+    for (int k = 0; k < kObsMaxTerms; k++) TL.t[k] = k < n ? terms[t0 + k] : obs_null_term();
+    double* part = d + (size_t)w * t0 * g;
+    if (vtype)
+      hipLaunchKernelGGL(k_expect<true>, dim3(g), dim3(kBlock), 0, st, s->d_map, (const double2*)vec_dev, s->dim,
+                         idx, TL, n, part);
+    else
+      hipLaunchKernelGGL(k_expect<false>, dim3(g), dim3(kBlock), 0, st, s->d_map, (const double*)vec_dev, s->dim,
+                         idx, TL, n, part);
+    HIPCK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_obs_finish, dim3((unsigned)nval), dim3(kBlock), 0, st, d, g, d + nval * g);
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(pin.p, d + nval * g, nval * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  const double* h = (const double*)pin.p;
+  for (int t = 0; t < nterm; t++) {
+    out[2 * t] = vtype ? h[2 * t] : h[t];
+    out[2 * t + 1] = vtype ? h[2 * t + 1] : 0.0;
+  }
   return ED_OK;
 }
 

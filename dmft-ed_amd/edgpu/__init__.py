@@ -9,6 +9,9 @@ Modules:
   diag        ed_diag sector loop (single GPU) and the T=0 state list
   farm        sector farm over ranks (torch.distributed / RCCL)
   gf          Green's functions (normal, nonSU2): device seeds, Lanczos, poles
+  observables impurity observables and local energies of the kept states
+              (observables_impurity / local_energy_impurity) from device
+              vectors: Sector.nn_moments / Sector.expect
   dist        one sector over ranks (row split + Allgatherv; Kronecker all-to-all)
 
 Importing this package does not touch the GPU; the HIP library is loaded on

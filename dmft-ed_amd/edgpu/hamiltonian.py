@@ -254,6 +254,60 @@ class Sector:
                                          ctypes.byref(nhv)), "ed_sector_eigh")
         return ev, (out.T if out is not None else None), int(nconv.value), int(nhv.value)
 
+    # ---------------------------------------------------------- observables
+    def _state_arg(self, vec):
+        """(vtype, device tensor, stream) of a state vector: a torch tensor on
+        this sector's GPU is used in place, a numpy array is uploaded."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        if isinstance(vec, np.ndarray):
+            cplx = np.iscomplexobj(vec)
+            vec = torch.from_numpy(np.ascontiguousarray(vec, dtype=np.complex128 if cplx else np.float64))
+        if vec.dtype not in (torch.float64, torch.complex128):
+            raise TypeError("vectors must be float64 or complex128")
+        x = vec.to(dev).contiguous()
+        if x.numel() != self.dim:
+            raise ValueError("state vector length != dim")
+        st = torch.cuda.current_stream(dev)
+        # torch's default stream reaches the library as NULL, which then runs on
+        # the sector's own non-blocking stream: the vector must be complete first
+        st.synchronize()
+        return (1 if x.is_complex() else 0), x, st
+
+    def nn_moments(self, vec, levels):
+        """Occupation pair moments of a state (ed_sector_nn_moments):
+        (M, norm) with M[p, q] = sum_i |v_i|^2 n_{levels[p]}(i) n_{levels[q]}(i)
+        (symmetric, M[p, p] = <n_p>) and norm = sum_i |v_i|^2, in one device
+        pass — what the diagonal loop of observables_impurity
+        (ED_OBSERVABLES.f90:127-158) accumulates.  Up to 6 levels (0-based bits)."""
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        n = len(lv)
+        vt, x, st = self._state_arg(vec)
+        out = np.zeros(n * (n + 1) // 2 + 1)
+        check(_lib.load().ed_sector_nn_moments(self._h, vt, _tptr(x), n, _ptr(lv), _ptr(out), _stream_ptr(st)),
+              "ed_sector_nn_moments")
+        M = np.zeros((n, n))
+        M[np.triu_indices(n)] = out[:-1]
+        M = M + np.triu(M, 1).T
+        return M, float(out[-1])
+
+    def expect(self, vec, terms):
+        """<v|T|v> of operator strings (ed_sector_expect): `terms` is a list of
+        lists of (level, op), op 0 = c and 1 = c^+, level the 0-based bit,
+        applied right to left (the last pair acts first); e.g.
+        [(p, 1), (q, 0)] is c^+_p c_q.  Returns a complex array, one value per
+        term.  A string that leaves the sector is refused (ED_ERR_ARG)."""
+        nops = np.array([len(t) for t in terms], dtype=np.int32)
+        flat = [lo for t in terms for lo in t]
+        lv = np.array([int(l) for l, _ in flat], dtype=np.int32)
+        op = np.array([int(o) for _, o in flat], dtype=np.int32)
+        vt, x, st = self._state_arg(vec)
+        out = np.zeros(2 * len(terms))
+        check(_lib.load().ed_sector_expect(self._h, vt, _tptr(x), len(terms), _ptr(nops), _ptr(lv), _ptr(op),
+                                           _ptr(out), _stream_ptr(st)), "ed_sector_expect")
+        return out[0::2] + 1j * out[1::2]
+
     def _out_array(self, shape, vt, on_device):
         if not on_device:
             return np.zeros(shape, dtype=np.complex128 if vt else np.float64)

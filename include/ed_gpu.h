@@ -33,6 +33,9 @@
  *   ed_gpu_lanc_eigh          <- sp_lanc_eigh (SciFortran; spec .repo/PLAIN_LANCZOS.f90:286-385)
  *   ed_gpu_lanc_tridiag       <- sp_lanc_tridiag (SciFortran; spec .repo/PLAIN_LANCZOS.f90:154-180)
  *   ed_gpu_eigh               <- sp_eigh (ARPACK; called at ED_DIAG.f90:145-167)
+ *   ed_sector_nn_moments      <- observables_impurity   ED_OBSERVABLES.f90:48-715 and
+ *   ed_sector_expect             local_energy_impurity  ED_OBSERVABLES.f90:726-980
+ *                                (their sums over the kept vector's elements)
  */
 #ifndef ED_GPU_H
 #define ED_GPU_H
@@ -321,6 +324,31 @@ int ed_sector_apply_op(const ed_sector* src, const ed_sector* dst, int32_t op, i
 int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t op, int32_t level,
                            double coef_re, double coef_im, int32_t vtype, const void* src_vec,
                            void* dst_vec, void* stream);
+/* Observables of a kept state from its device-resident vector
+ * (observables_impurity ED_OBSERVABLES.f90:48-715, local_energy_impurity
+ * ED_OBSERVABLES.f90:726-980; no host copy of the vector, no bdecomp /
+ * binary_search per element).
+ *
+ * Occupation pair moments — the diagonal loops ED_OBSERVABLES.f90:127-158 and
+ * the density-density / Hartree sums ED_OBSERVABLES.f90:797-943 are linear in them:
+ * M[p][q] = sum_i |v_i|^2 n_{levels[p]}(i) n_{levels[q]}(i), p <= q, packed row-major upper
+ * triangle (nlev*(nlev+1)/2 doubles), followed by one more double: sum_i |v_i|^2.
+ * nlev <= 2*ED_MAX_NORB.  Any whole sector (stored or direct).  out: host.  Synchronous on
+ * stream (NULL: the sector's own). */
+int ed_sector_nn_moments(const ed_sector* s, int32_t vtype, const void* vec_dev,
+                         int32_t nlev, const int32_t* levels, double* out, void* stream);
+/* Expectation values of operator strings — the off-diagonal sums
+ * ED_OBSERVABLES.f90:556-581 (impurity density matrix), :631-654 (bath),
+ * :802-846 (hopping energy), :882-927 (spin exchange, pair hopping) and the
+ * magX / magY / phisc seeds :166-337 expanded:
+ * out[t] = <v| T_t |v> = sum_i conj(v_{j(i)}) * sign * v_i  for nterm operator strings;
+ * nops[t] in 1..4, levels/ops concatenated (op 0 = c, 1 = c^+; level the 0-based bit, as
+ * ed_sector_apply_op), applied right to left.
+ * out: 2*nterm doubles (re, im), host; vtype = 0 gives im = 0.  A term that leaves the
+ * sector: ED_ERR_ARG, nothing launched.  Row-split sectors: ED_ERR_UNSUPPORTED. */
+int ed_sector_expect(const ed_sector* s, int32_t vtype, const void* vec_dev, int32_t nterm,
+                     const int32_t* nops, const int32_t* levels, const int32_t* ops,
+                     double* out, void* stream);
 /* sp_lanc_tridiag from a device start vector (not modified). */
 /* v0_dev must be complete on entry (synchronise the stream that wrote it). */
 int ed_sector_lanc_tridiag_dev(ed_sector* s, int32_t vtype, const void* v0_dev, int32_t nitermax,
