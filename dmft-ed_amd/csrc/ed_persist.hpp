@@ -20,8 +20,12 @@
 //     down-hop gathers of a wavefront are contiguous;
 //   * alpha and beta are block reductions (DPP wave sums + one LDS stage),
 //     two barriers per iteration, no global synchronisation.
-// configs[1]: MODE 4 1.87 µs per step with the slot-major LDS vector below
-// (2.24 before it; MODE 2 4.4 µs before the Kronecker layout).
+// configs[1]: MODE 4 1.64 µs per step (1.85-1.87 with 35 more VALU
+// instructions per wave and step and the next step's first gathers behind
+// beta's square root; 2.24 before the slot-major LDS vector below; MODE 2
+// 4.4 µs before the Kronecker layout).  The step is bound by instruction
+// issue: VALU and LDS instructions of a SIMD's two waves hardly overlap
+// (profiles/persist_mode4/INDEX.md), so an instruction removed is time won.
 #pragma once
 #include "ed_kernels.hpp"
 
@@ -70,12 +74,17 @@ struct PersistRun {
 };
 
 // Wave sum on DPP row operations (no LDS traffic, ~6 dependent VALU steps
-// instead of 6 ds_bpermute round trips); the total lands in lane 63.
+// instead of 6 ds_bpermute round trips); the total lands in lane 63, the
+// only lane a caller may read.
 template <int CTRL, int RM>
 __device__ __forceinline__ double dpp_add(double v) {
   const int lo = __double2loint(v), hi = __double2hiint(v);
-  const int l2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, RM, 0xF, false);
-  const int h2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, RM, 0xF, false);
+  // mov_dpp, not update_dpp with a zero to fall back on (two v_mov_b32 per
+  // level): the row operations write every lane from a valid source lane, and
+  // the two row_bcast levels leave the rows outside their row mask undefined,
+  // none of which feeds lane 63
+  const int l2 = __builtin_amdgcn_mov_dpp(lo, CTRL, RM, 0xF, true);
+  const int h2 = __builtin_amdgcn_mov_dpp(hi, CTRL, RM, 0xF, true);
   return v + __hiloint2double(h2, l2);
 }
 __device__ __forceinline__ double wave_sum_dpp(double v) {
@@ -453,6 +462,20 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
   double* const beta_out = a.beta + run * a.ldab;
   V* const basis = run == 0 ? (V*)a.basis : nullptr;
 
+  // PIPE: one row's gathers (up hops, down hops, own entry)
+  double gu[PIPE ? E : 1], gd[PIPE ? E : 1], go = 0.0;
+  auto gather = [&](int r, double* hu, double* hd, double& ho) {
+    if constexpr (PIPE) {
+#pragma unroll
+      for (int e = 0; e < E; e++) hu[e] = lds_ldv<double>(ucol[e] + r * VSLOT * 8);  // slot r of row iw
+#pragma unroll
+      for (int e = 0; e < E; e++) hd[e] = lds_ldv<double>(dcol[r * E + e]);
+      if constexpr (UREG) ho = u[r];
+      else ho = vl[LPOS(r)];
+    }
+  };
+  gather(0, gu, gd, go);
+
   for (int k = 0; k < a.niter; k++) {
     const int it = it0 + k;
     if constexpr (REG) {
@@ -475,17 +498,12 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
       // MODE 4: software-pipelined gathers — row r+1's 2E LDS reads are in
       // flight while row r is summed (issued per hop group of 4 and waited
       // at once, one wave had <= 4 reads outstanding: the LDS latency was
-      // exposed ~20 times per step at 2 waves per SIMD)
-      double gu[E], gd[E], go;
-      auto gather = [&](int r, double* hu, double* hd, double& ho) {
-#pragma unroll
-        for (int e = 0; e < E; e++) hu[e] = lds_ldv<double>(ucol[e] + r * VSLOT * 8);  // slot r of row iw
-#pragma unroll
-        for (int e = 0; e < E; e++) hd[e] = lds_ldv<double>(dcol[r * E + e]);
-        if constexpr (UREG) ho = u[r];
-        else ho = vl[LPOS(r)];
-      };
-      gather(0, gu, gd, go);
+      // exposed ~20 times per step at 2 waves per SIMD); row 0's reads were
+      // issued behind the previous step's beta barrier.
+      // (A rolling window of 12-16 reads per wave from asm statements with
+      // counted waits, lgkmcnt(0) on the last rows only, measured slower: a
+      // wait, a pad and a read per FMA cost more issue slots than the
+      // latency they hide; profiles/persist_mode4/INDEX.md.)
 #pragma unroll
       for (int r = 0; r < RPT; r++) {
         double nu[E], nd[E], no = 0.0;
@@ -501,9 +519,15 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
         // contracted recurrence (MODE 4 already fuses its gathers; the
         // Lanczos bar is 1e-10, not bit-exactness): f64 VALU issue is a
         // large part of the step at 2 waves per SIMD
-        const double x = s * ur;
-        w[r] = fma(s, acc, -(b * p[r]));
-        ap = fma(x, w[r], ap);
+        // p's old value ends in b * p, formed first (the empty asm pins it
+        // there, else p is copied: 10 v_mov_b64); v_k = s * r_k then takes
+        // p's register, so the second half of the step neither re-reads its
+        // own rows from LDS nor forms the product again
+        double bpr = b * p[r];
+        asm volatile("" : "+v"(bpr));
+        p[r] = s * ur;
+        w[r] = fma(s, acc, -bpr);
+        ap = fma(p[r], w[r], ap);
         if (r + 1 < RPT) {
 #pragma unroll
           for (int e = 0; e < E; e++) {
@@ -610,12 +634,14 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
     if (basis) {  // uniform: no per-row EXEC masking when no basis is kept
 #pragma unroll
       for (int r = 0; r < RPT; r++)
-        if (r < q.nvalid) basis[(int64_t)it * dim + PROW(r)] = scl(s, UREG ? u[r] : vl[LPOS(r)]);  // column k = v_k
+        if (r < q.nvalid) basis[(int64_t)it * dim + PROW(r)] = PIPE ? p[r] : scl(s, UREG ? u[r] : vl[LPOS(r)]);  // column k = v_k
     }
 #pragma unroll
     for (int r = 0; r < RPT; r++) {
       const int i = PROW(r);
-      const V x = scl(s, UREG ? u[r] : vl[LPOS(r)]);
+      V x;
+      if constexpr (PIPE) x = p[r];
+      else x = scl(s, UREG ? u[r] : vl[LPOS(r)]);
       if constexpr (PIPE) {
         w[r] = fma(-alpha, x, w[r]);
         bp = fma(w[r], w[r], bp);
@@ -625,7 +651,7 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
       }
       if constexpr (PG) {
         Pg[i] = x;
-      } else {
+      } else if constexpr (!PIPE) {
         p[r] = x;
       }
       if constexpr (UREG) u[r] = w[r];
@@ -634,9 +660,21 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
     // beta barrier: also publishes r_{k+1}
 #ifdef ED_P4_NOBETA  // timing probe: the step without the beta reduction (a bare barrier)
     __syncthreads();
-    const double bn = 1.0 + bp * 1e-300;
+    const double bsq = 1.0 + bp * 1e-300;
 #else
-    const double bn = sqrt(pblock_sum<NT, false>(bp, ws2));
+    const double bsq = pblock_sum<NT, false>(bp, ws2);
+#endif
+    if constexpr (PIPE) {
+      // r_{k+1} is published: the next step's first row of gathers goes out
+      // ahead of the square root and the reciprocal (~30 dependent f64
+      // instructions that need no LDS)
+      gather(0, gu, gd, go);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#ifdef ED_P4_NOBETA
+    const double bn = bsq;
+#else
+    const double bn = sqrt(bsq);
 #endif
     if (tid == 0) {
       alpha_out[it] = alpha;
