@@ -48,6 +48,7 @@ static inline int persist_rpt01(int64_t dim) {
 struct PersistGeom {
   int64_t dim = 0;
   int preg_E = 0, preg_rpt = 0, kreg_W = 0, kreg_rpt = 0, pkr_E = 0, pkr_rpt = 0;
+  int device = 0;  // the sector's device (the dynamic-LDS attribute is set once per kernel and device)
 };
 
 // Launch k_lanc_persist for (hc, vc, mode) on the geometry's template values;

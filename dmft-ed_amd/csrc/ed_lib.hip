@@ -95,7 +95,7 @@ struct LancWS {
   double* partials = nullptr;   // [kMaxGrid]
   unsigned int* counter = nullptr;
   double *alpha = nullptr, *beta = nullptr, *z = nullptr;  // one block: alpha | beta | z, cap+2 each
-  double* h_ab = nullptr;       // pinned host staging for alpha | beta (2*(cap+2))
+  double* h_ab = nullptr;       // pinned host staging for alpha | beta (2*(cap+2)); the persistent kernel of a single run writes it directly
   hipEvent_t ev[2] = {nullptr, nullptr};  // lanc_run timing
   void* basis = nullptr;
   int basis_cols = 0;
@@ -180,6 +180,12 @@ struct ed_sector {
   std::vector<void*> allocs;
   // persistent one-workgroup Lanczos (small sectors)
   double pthresh = 0.0;     // breakdown threshold of the current persistent run
+  // the last persist_mode answer and its LDS bytes, valid for (vc, path, opts);
+  // one entry: the mode's tables (MODE 4: per path) are those of the last answer
+  struct {
+    int vc = -1, path = -3, opts = 0, mode = -1;
+    int64_t lds = 0;
+  } pchoice;
   // register-resident stored matrix for the persistent kernel (MODE 2)
   int preg_E = 0;           // 0 not built, -1 ineligible, else ELL row width W
   int preg_rpt = 0;         // rows per thread (template value)
@@ -261,7 +267,7 @@ static void* pinned_get(size_t n) {
   }
   n = std::max<size_t>(n, 4096);
   void* p = nullptr;
-  if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) return nullptr;
+  if (hipHostMalloc(&p, n, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) return nullptr;
   std::lock_guard<std::mutex> lk(g_pin_mu);
   g_pin_size[p] = n;
   return p;
@@ -2112,7 +2118,7 @@ static int64_t persist_vrows(const ed_sector* s, int mode, int vc = 0) {
   }
 }
 // ELL words per lane that compile without scratch (-Rpass-analysis=kernel-resource-usage)
-static int persist_mode(ed_sector* s, int vc, int path) {
+static int persist_mode_derive(ed_sector* s, int vc, int path) {
   const int o = s->opts;
   if (o & ED_OPT_NO_PERSIST) return -1;
   const int64_t vs = vc ? 16 : 8;
@@ -2204,6 +2210,22 @@ static int64_t persist_lds(const ed_sector* s, int vc, int mode) {
   return lds;
 }
 
+// The mode for (vc, path) under the sector's options, derived once: every
+// Lanczos entry point asks on every call, and the answer (with the tables it
+// builds) changes only with these three (ed_sector_set_options drops it).
+static int persist_mode(ed_sector* s, int vc, int path) {
+  auto& c = s->pchoice;
+  if (c.vc == vc && c.path == path && c.opts == s->opts) return c.mode;
+  c.vc = -1;  // not valid while the tables are rebuilt
+  const int mode = persist_mode_derive(s, vc, path);
+  c.lds = mode >= 0 ? persist_lds(s, vc, mode) : 0;
+  c.mode = mode;
+  c.path = path;
+  c.opts = s->opts;
+  c.vc = vc;
+  return mode;
+}
+
 static PersistGeom persist_geom(const ed_sector* s) {
   PersistGeom g;
   g.dim = s->dim;
@@ -2213,6 +2235,7 @@ static PersistGeom persist_geom(const ed_sector* s) {
   g.kreg_rpt = s->kreg_rpt;
   g.pkr_E = s->pkr_E;
   g.pkr_rpt = s->pkr_rpt;
+  g.device = s->device;
   return g;
 }
 
@@ -2226,10 +2249,17 @@ struct PersistBatch {
   int64_t ldr, ldp, ldab;
 };
 
-// Launch `niter` persistent iterations.  first=1 starts from the vector in R.
+// Launch `niter` persistent iterations.  first=1 starts from the device
+// vector v0 (only read; batched: run b at v0 + b*dim), or from R when v0 is
+// null.  A first launch needs nothing prepared on the stream: the kernel
+// initialises the LancState, beta[0] and, on an early stop, the zeros behind
+// the last step.  host_ab: the kernel's one lane stores alpha and beta of each
+// step straight into the pinned staging block w.h_ab (alpha | beta at cap + 2;
+// device-visible host memory, two 8-B stores per step that nothing waits
+// for), so no download of them follows the run.
 template <bool VC>
 static int persist_iters(ed_sector* s, int mode, bool basis, int niter, int first, hipStream_t st,
-                         const PersistBatch* bt = nullptr) {
+                         const PersistBatch* bt = nullptr, const void* v0 = nullptr, bool host_ab = false) {
   LancWS& w = s->ws;
   const int nb = bt ? bt->nb : 1;
   auto fill = [&](auto& r) {
@@ -2242,10 +2272,11 @@ static int persist_iters(ed_sector* s, int mode, bool basis, int niter, int firs
     r.vals = (const HT*)s->d_vals;
     r.dim = s->dim;
     r.R = w.R;
+    r.v0 = first ? v0 : nullptr;
     r.P = w.P;
     r.st = w.st;
-    r.alpha = w.alpha;
-    r.beta = w.beta;
+    r.alpha = host_ab ? w.h_ab : w.alpha;
+    r.beta = host_ab ? w.h_ab + w.cap + 2 : w.beta;
     r.basis = basis ? w.basis : nullptr;
     r.niter = niter;
     r.first = first;
@@ -2274,7 +2305,8 @@ static int persist_iters(ed_sector* s, int mode, bool basis, int niter, int firs
       r.ldab = bt->ldab;
     }
   };
-  const int64_t lds = persist_lds(s, VC, mode);
+  const auto& pc = s->pchoice;
+  const int64_t lds = (pc.vc == (int)VC && pc.mode == mode) ? pc.lds : persist_lds(s, VC, mode);
   if (s->hc) {
     if constexpr (!VC) return fail(ED_ERR_ARG, "complex H needs complex vectors");
     else {
@@ -2292,11 +2324,11 @@ static int persist_iters(ed_sector* s, int mode, bool basis, int niter, int firs
 }
 
 static int persist_set_thresh(ed_sector* s, double thresh, hipStream_t st) {
-  // stream-ordered, no host sync: the threshold travels in the kernel
-  // argument, the kernel initialises the LancState fields on its first launch
+  // nothing on the stream: the threshold travels in the kernel argument; the
+  // first launch initialises the LancState, writes beta[0] = 0 and, when it
+  // stops early, the zeros behind its last step (k_lanc_persist)
+  (void)st;
   s->pthresh = thresh;
-  HIPCK(hipMemsetAsync(s->ws.st, 0, sizeof(LancState), st));
-  HIPCK(hipMemsetAsync(s->ws.alpha, 0, 2 * (s->ws.cap + 2) * sizeof(double), st));  // alpha | beta
   return ED_OK;
 }
 
@@ -3579,7 +3611,10 @@ static constexpr int32_t kOptKnown =
 int ed_sector_set_options(ed_sector* s, int32_t opts) {
   if (!s) return fail(ED_ERR_ARG, "null");
   if (opts & ~kOptKnown) return fail(ED_ERR_ARG, "unknown ED_OPT_* bits");
-  if (opts != s->opts) drop_graph(s);  // a captured recurrence bakes in the kernel choice
+  if (opts != s->opts) {
+    drop_graph(s);  // a captured recurrence bakes in the kernel choice
+    s->pchoice.vc = -1;  // and the persistent mode is chosen anew
+  }
   s->opts = opts;
   return ED_OK;
 }
@@ -3741,6 +3776,8 @@ int ed_sector_sell_view(const ed_sector* s, ed_sell_view* v) {
 
 // One Lanczos driver for every entry point: persistent one-workgroup kernel
 // when the sector fits a CU, graph-captured two-kernel recurrence otherwise.
+static int lanc_load_start(ed_sector* s, int vc, const void* v0, bool v0_device);
+
 struct LancDriver {
   ed_sector* s;
   int vc, path, pm;
@@ -3750,11 +3787,41 @@ struct LancDriver {
     if (pm >= 0) return persist_set_thresh(s, thresh, st);
     return vc ? lanc_start<true>(s, thresh, st) : lanc_start<false>(s, thresh, st);
   }
-  int iters(int n, bool first) {
-    if (pm >= 0)
-      return vc ? persist_iters<true>(s, pm, basis, n, first ? 1 : 0, st)
-                : persist_iters<false>(s, pm, basis, n, first ? 1 : 0, st);
+  // v0 (persistent kernel, first launch): a device start vector read in
+  // place; null: the vector lanc_load_start left in ws.R
+  int iters(int n, bool first, const void* v0 = nullptr) {
+    if (pm >= 0)  // alpha and beta land in the pinned staging block (fetch)
+      return vc ? persist_iters<true>(s, pm, basis, n, first ? 1 : 0, st, nullptr, v0, true)
+                : persist_iters<false>(s, pm, basis, n, first ? 1 : 0, st, nullptr, v0, true);
     return vc ? lanc_iters<true>(s, path, basis, n, st) : lanc_iters<false>(s, path, basis, n, st);
+  }
+  // alpha[0, na), beta[0, nb) and the LancState of the run so far, behind one
+  // host sync.  Persistent kernel: alpha and beta are already in host memory
+  // (the staging block), only the state is downloaded.
+  int fetch(double* a, int na, double* b, int nb, LancState* hs) {
+    LancWS& w = s->ws;
+    if (pm < 0) {
+      HIPCK(hipMemcpyAsync(a, w.alpha, (size_t)na * 8, hipMemcpyDeviceToHost, st));
+      HIPCK(hipMemcpyAsync(b, w.beta, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIPCK(hipMemcpyAsync(hs, w.st, sizeof(*hs), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (pm >= 0) {
+      memcpy(a, w.h_ab, (size_t)na * 8);
+      memcpy(b, w.h_ab + w.cap + 2, (size_t)nb * 8);
+    }
+    return ED_OK;
+  }
+  // Start vector of a run: a device vector stays where it is when the
+  // persistent kernel takes the run (returned for iters); otherwise it is
+  // loaded into ws.R
+  int load(const void* v0, bool v0_device, const void** inplace) {
+    *inplace = nullptr;
+    if (pm >= 0 && v0 && v0_device) {
+      *inplace = v0;
+      return ED_OK;
+    }
+    return lanc_load_start(s, vc, v0, v0_device);
   }
 };
 
@@ -3792,7 +3859,11 @@ int ed_sector_lanc_run(ed_sector* s, int32_t vtype, const void* v0_dev, int32_t 
   LancDriver d;
   CK(make_driver(s, vtype, false, &d));
   CK(lanc_prepare(s, d.vc, niter, false, 0));
-  CK(lanc_load_start(s, d.vc, v0_dev, true));
+  // persistent kernel: the stream gets the two event records and one kernel
+  // (the start vector is read in place, nothing is cleared, alpha and beta
+  // land in the staging block)
+  const void* v0p = nullptr;
+  CK(d.load(v0_dev, true, &v0p));
   LancWS& w = s->ws;
   for (hipEvent_t& e : w.ev)
     if (!e) HIPCK(hipEventCreate(&e));
@@ -3800,12 +3871,13 @@ int ed_sector_lanc_run(ed_sector* s, int32_t vtype, const void* v0_dev, int32_t 
   int rc = d.start(1e-300);
   if (rc == ED_OK) {
     HIPCK(hipEventRecord(e0, d.st));
-    rc = d.iters(niter, true);
+    rc = d.iters(niter, true, v0p);
     HIPCK(hipEventRecord(e1, d.st));
   }
-  // one host sync for the run and one pinned copy of alpha | beta
+  // one host sync for the run; the multi-kernel recurrence downloads
+  // alpha | beta into the staging block, the persistent kernel wrote them there
   const size_t nab = (size_t)w.cap + 2 + niter;
-  if (rc == ED_OK && (alfa || beta))
+  if (rc == ED_OK && (alfa || beta) && d.pm < 0)
     HIPCK(hipMemcpyAsync(w.h_ab, w.alpha, nab * sizeof(double), hipMemcpyDeviceToHost, d.st));
   HIPCK(hipStreamSynchronize(d.st));
   CK(rc);
@@ -3826,11 +3898,8 @@ int ed_sector_lanc_tridiag(ed_sector* s, int32_t vtype, const void* v0, int32_t 
   CK(d.start(threshold));
   CK(d.iters(nitermax, true));
   std::vector<double> a(nitermax + 1), b(nitermax + 2);
-  HIPCK(hipMemcpyAsync(a.data(), s->ws.alpha, nitermax * 8, hipMemcpyDeviceToHost, d.st));
-  HIPCK(hipMemcpyAsync(b.data(), s->ws.beta, (nitermax + 1) * 8, hipMemcpyDeviceToHost, d.st));
   LancState hs;
-  HIPCK(hipMemcpyAsync(&hs, s->ws.st, sizeof(hs), hipMemcpyDeviceToHost, d.st));
-  HIPCK(hipStreamSynchronize(d.st));
+  CK(d.fetch(a.data(), nitermax, b.data(), nitermax + 1, &hs));
   // lanczos_plain_tridiag_c: alanc(iter)=a; if(iter<nitermax)blanc(iter+1)=b; exit if |b|<thr
   int n = hs.iter;
   for (int q = 0; q < nitermax; q++) {
@@ -3868,15 +3937,13 @@ int ed_sector_lanc_tridiag_batch(ed_sector* s, int32_t vtype, int32_t nseed, con
   if (d.pm < 0 || (s->opts & ED_OPT_NO_BATCH)) {
     CK(lanc_prepare(s, d.vc, nitermax, false, 0));
     for (int k = 0; k < nseed; k++) {
-      CK(lanc_load_start(s, d.vc, (const unsigned char*)v0_dev + (size_t)k * s->dim * vs, true));
+      const void* v0p = nullptr;
+      CK(d.load((const unsigned char*)v0_dev + (size_t)k * s->dim * vs, true, &v0p));
       CK(d.start(threshold));
-      CK(d.iters(nitermax, true));
+      CK(d.iters(nitermax, true, v0p));
       std::vector<double> a(nitermax + 1), b(nitermax + 2);
       LancState hs;
-      HIPCK(hipMemcpyAsync(a.data(), s->ws.alpha, nitermax * 8, hipMemcpyDeviceToHost, d.st));
-      HIPCK(hipMemcpyAsync(b.data(), s->ws.beta, (nitermax + 1) * 8, hipMemcpyDeviceToHost, d.st));
-      HIPCK(hipMemcpyAsync(&hs, s->ws.st, sizeof(hs), hipMemcpyDeviceToHost, d.st));
-      HIPCK(hipStreamSynchronize(d.st));
+      CK(d.fetch(a.data(), nitermax, b.data(), nitermax + 1, &hs));
       unpack(k, a.data(), b.data(), hs.iter);
     }
     return ED_OK;
@@ -3905,15 +3972,11 @@ int ed_sector_lanc_tridiag_batch(ed_sector* s, int32_t vtype, int32_t nseed, con
   bt.alpha = (double*)ab;
   bt.beta = (double*)ab + nitermax + 2;
   s->pthresh = threshold;
-  int rc = ED_OK;
-  if (hipMemcpyAsync(R, v0_dev, (size_t)nseed * s->dim * vs, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-      hipMemsetAsync(P, 0, (size_t)nseed * bt.ldp * vs, st) != hipSuccess ||
-      hipMemsetAsync(ab, 0, (size_t)nseed * bt.ldab * 8, st) != hipSuccess ||
-      hipMemsetAsync(sts, 0, (size_t)nseed * sizeof(LancState), st) != hipSuccess)
-    rc = fail(ED_ERR_HIP, "batch workspace");
-  if (rc == ED_OK)
-    rc = d.vc ? persist_iters<true>(s, d.pm, false, nitermax, 1, st, &bt)
-              : persist_iters<false>(s, d.pm, false, nitermax, 1, st, &bt);
+  // one kernel: every run reads its seed in place (run b at v0_dev + b*dim,
+  // ldr = dim), starts from p = 0 and initialises its own LancState, beta[0]
+  // and, on an early stop, its alpha / beta tail
+  int rc = d.vc ? persist_iters<true>(s, d.pm, false, nitermax, 1, st, &bt, v0_dev)
+                : persist_iters<false>(s, d.pm, false, nitermax, 1, st, &bt, v0_dev);
   std::vector<double> hab((size_t)nseed * bt.ldab);
   std::vector<LancState> hst(nseed);
   if (rc == ED_OK) {
@@ -4171,15 +4234,13 @@ int ed_sector_lanc_tridiag_dev(ed_sector* s, int32_t vtype, const void* v0_dev, 
   // v0_dev must be complete when this is called (the caller synchronises the
   // stream that produced it): no device-wide sync, which would fail while
   // another host thread captures a graph on its own sector stream
-  CK(lanc_load_start(s, d.vc, v0_dev, true));
+  const void* v0p = nullptr;
+  CK(d.load(v0_dev, true, &v0p));
   CK(d.start(threshold));
-  CK(d.iters(nitermax, true));
+  CK(d.iters(nitermax, true, v0p));
   std::vector<double> a(nitermax + 1), b(nitermax + 2);
-  HIPCK(hipMemcpyAsync(a.data(), s->ws.alpha, nitermax * 8, hipMemcpyDeviceToHost, d.st));
-  HIPCK(hipMemcpyAsync(b.data(), s->ws.beta, (nitermax + 1) * 8, hipMemcpyDeviceToHost, d.st));
   LancState hs;
-  HIPCK(hipMemcpyAsync(&hs, s->ws.st, sizeof(hs), hipMemcpyDeviceToHost, d.st));
-  HIPCK(hipStreamSynchronize(d.st));
+  CK(d.fetch(a.data(), nitermax, b.data(), nitermax + 1, &hs));
   int n = hs.iter;
   for (int q = 0; q < nitermax; q++) {
     alfa[q] = q < n ? a[q] : 0.0;
@@ -4216,11 +4277,8 @@ int ed_sector_lanc_eigh(ed_sector* s, int32_t vtype, const void* v0, int32_t nit
     int n = std::min(chunk, nitermax - done_iters);
     const int expected = done_iters + n;
     CK(d.iters(n, done_iters == 0));
-    HIPCK(hipMemcpyAsync(a.data(), s->ws.alpha, nitermax * 8, hipMemcpyDeviceToHost, d.st));
-    HIPCK(hipMemcpyAsync(b.data(), s->ws.beta, (nitermax + 1) * 8, hipMemcpyDeviceToHost, d.st));
     LancState hs;
-    HIPCK(hipMemcpyAsync(&hs, s->ws.st, sizeof(hs), hipMemcpyDeviceToHost, d.st));
-    HIPCK(hipStreamSynchronize(d.st));
+    CK(d.fetch(a.data(), nitermax, b.data(), nitermax + 1, &hs));
     int have = hs.iter;
     for (int it = done_iters + 1; it <= have && !stop; it++) {
       // iteration `it`: a = a[it-1], b = b[it]

@@ -26,6 +26,16 @@
 // 4.4 µs before the Kronecker layout).  The step is bound by instruction
 // issue: VALU and LDS instructions of a SIMD's two waves hardly overlap
 // (profiles/persist_mode4/INDEX.md), so an instruction removed is time won.
+// Waves w and w + 4 of the 512-thread workgroup share a SIMD; a static or
+// per-phase priority for one of them and a de-phased start behind the beta
+// barrier were measured and lost; the row loop's reads spread in groups of 4
+// among the FMAs (sched_group_barrier) won 0.5-1.1 %, below the project's bar
+// in two sessions of three, and are not kept
+// (profiles/persist_sched/INDEX.md).
+// A run is one kernel: a first launch reads the caller's start vector in
+// place (PersistRun::v0), initialises the LancState and beta[0], and on an
+// early stop (breakdown, zero start vector) writes the zeros behind its last
+// step; nothing is copied or cleared ahead of it.
 #pragma once
 #include "ed_kernels.hpp"
 
@@ -46,7 +56,8 @@ struct PersistRun {
   // Kronecker tables (MODE 1, 3; MODE 4 direct diagonal)
   KronArgs<HC> K;
   int64_t dim;
-  void* R;           // in: start vector (first) or saved unnormalised r_k; out: saved r_k
+  void* R;           // in: start vector (first, v0 null) or saved unnormalised r_k; out: saved r_k
+  const void* v0;    // first: the caller's start vector, read in place (run b at v0 + b*ldr); null: R
   void* P;           // saved p = v_{k-1}
   LancState* st;     // beta (norm of R), iter, done
   double* alpha;     // [niter_total]
@@ -170,6 +181,19 @@ __device__ __forceinline__ PRows persist_rows(int tid, int64_t dim, int du, int 
     q.nvalid = dim > tid ? (int)((dim - tid + NT - 1) / NT) : 0;
   }
   return q;
+}
+
+// A run that stops early (breakdown, zero start vector) leaves zeros behind
+// its last step, as the reference's preset alanc / blanc do: alpha[j] and
+// beta[j + 1] for j in [from, end).  The kernel owns both arrays (no memset
+// ahead of the launch); this sits on the exit branches only, where the
+// iteration loop's registers are dead.
+template <int NT>
+__device__ __forceinline__ void persist_clear_tail(double* alpha, double* beta, int from, int end) {
+  for (int j = from + (int)threadIdx.x; j < end; j += NT) {
+    alpha[j] = 0.0;
+    beta[j + 1] = 0.0;
+  }
 }
 
 // One-workgroup plain Lanczos (.repo/PLAIN_LANCZOS.f90:87-118):
@@ -416,13 +440,18 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
   uint32_t rix[RPT];    // Kronecker row index packed (iw << 16) | iu  (DimUp, DimDw < 2^16)
   double b, s;          // b_k and 1/b_k (s = 1/|r_0| on the first step, b_0 = 0)
   int it0;
+  double* const alpha_out = a.alpha + run * a.ldab;
+  double* const beta_out = a.beta + run * a.ldab;
   {
+    // first launch: the caller's start vector is read where it lies (no copy
+    // into R; R is written at state out only)
+    const V* const Sg = (a.first && a.v0) ? (const V*)a.v0 + run * a.ldr : Rg;
     double nrm = 0.0;
 #pragma unroll
     for (int r = 0; r < RPT; r++) {
       const int i = PROW(r);
       const bool ok = r < q.nvalid;
-      const V x = ok ? Rg[i] : vzero<V>();
+      const V x = ok ? Sg[i] : vzero<V>();
       if constexpr (UREG) u[r] = x;
       vl[LPOS(r)] = x;
       if constexpr (!PG) p[r] = (ok && !a.first) ? Pg[i] : vzero<V>();
@@ -438,7 +467,8 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
     if (a.first) {
       const double n2 = pblock_sum<NT>(nrm, ws);
       if (n2 == 0.0) {                  // lanczos_plain_iteration: "norm =0!!"
-        if (tid == 0) { st->iter = 0; st->done = 1; st->beta = 0.0; }
+        if (tid == 0) { st->iter = 0; st->done = 1; st->beta = 0.0; beta_out[0] = 0.0; }
+        persist_clear_tail<NT>(alpha_out, beta_out, 0, a.niter);
         return;
       }
       s = 1.0 / sqrt(n2);
@@ -448,6 +478,7 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
         st->iter = 0;
         st->done = 0;
         st->beta = 0.0;
+        beta_out[0] = 0.0;
       }
     } else {
       b = st->beta;
@@ -458,8 +489,6 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
   }
   if (st->done && !a.first) return;
   const double thresh = a.thresh;
-  double* const alpha_out = a.alpha + run * a.ldab;
-  double* const beta_out = a.beta + run * a.ldab;
   V* const basis = run == 0 ? (V*)a.basis : nullptr;
 
   // PIPE: one row's gathers (up hops, down hops, own entry)
@@ -688,6 +717,7 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
         st->iter = it + 1;
         st->beta = bn;
       }
+      persist_clear_tail<NT>(alpha_out, beta_out, it + 1, it0 + a.niter);
       return;
     }
   }

@@ -2,11 +2,16 @@
 // persistent Lanczos, ed_persist.hpp) and their dispatch on the sector's
 // register-layout geometry.  A translation unit of its own: these ~150
 // instantiations are half of the library's device compile.
+#include <atomic>
+#include <mutex>
+
 #include "ed_host.hpp"
 #include "ed_kernels.hpp"
 #include "ed_persist.hpp"
 
 namespace edg {
+
+constexpr int kMaxDevices = 64;  // device ordinals with a remembered dynamic-LDS limit
 
 template <bool HC, bool VC, int MODE, int RPT, int E = 1>
 static int persist_launch_t(const PersistGeom& s, const PersistRun<HC>& run, int64_t lds, hipStream_t st, int nb) {
@@ -17,7 +22,21 @@ static int persist_launch_t(const PersistGeom& s, const PersistRun<HC>& run, int
   } else {
   constexpr int NT = MODE >= 2 ? kPRegBlock : kPBlock;
   auto fn = k_lanc_persist<HC, VC, MODE, RPT, E, NT>;
-  HIPCK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // the dynamic-LDS limit of this instantiation on this device: raised when
+  // a launch needs more than any before it, not set on every launch (host
+  // threads raise it under the lock, so the last value set is the largest)
+  static std::atomic<int64_t> lds_set[kMaxDevices];
+  static std::mutex mu;
+  const int dev = s.device;
+  if (dev < 0 || dev >= kMaxDevices) {
+    HIPCK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  } else if (lds > lds_set[dev].load(std::memory_order_acquire)) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (lds > lds_set[dev].load(std::memory_order_relaxed)) {
+      HIPCK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      lds_set[dev].store(lds, std::memory_order_release);
+    }
+  }
   hipLaunchKernelGGL(fn, dim3(nb), dim3(NT), (size_t)lds, st, run);
   HIPCK(hipGetLastError());
   return ED_OK;
