@@ -20,7 +20,9 @@
 //     down-hop gathers of a wavefront are contiguous;
 //   * alpha and beta are block reductions (DPP wave sums + one LDS stage),
 //     two barriers per iteration, no global synchronisation.
-// configs[1]: MODE 4 1.64 µs per step (1.85-1.87 with 35 more VALU
+// configs[1]: MODE 4 1.57 µs per step (1.64-1.66 with the own rows of r_k
+// re-read from LDS, 10 ds_read_b64 more per wave and step,
+// profiles/persist_ownrows/INDEX.md; 1.85-1.87 with 35 more VALU
 // instructions per wave and step and the next step's first gathers behind
 // beta's square root; 2.24 before the slot-major LDS vector below; MODE 2
 // 4.4 µs before the Kronecker layout).  The step is bound by instruction
@@ -431,10 +433,11 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
   constexpr bool PG = (REG || KRC) && VC;
   // real vectors keep their own rows of r_k in registers; complex ones
   // re-read them from LDS (register budget of the ELL words)
-  // (MODE 4 at 10 rows per thread reads them from LDS with the gathers: the
-  // software-pipelined gathers need the 20 VGPRs)
+  // (the software-pipelined MODE 4 loop at 10 rows per thread included: u[r]
+  // is last read in row r, where w[r] is first written, so w lives in u's
+  // registers and the own rows cost no VGPR beyond w's)
   constexpr bool PIPE = KR && !VC && RPT * E <= 40;  // software-pipelined MODE 4 gathers (spill-free)
-  constexpr bool UREG = !VC && (REG || (KR && (!PIPE || RPT * E < 40)));
+  constexpr bool UREG = !VC && (REG || KR);
   V u[UREG ? RPT : 1];  // own rows of r_k (the LDS vector)
   V p[PG ? 1 : RPT];
   uint32_t rix[RPT];    // Kronecker row index packed (iw << 16) | iu  (DimUp, DimDw < 2^16)
@@ -491,19 +494,19 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
   const double thresh = a.thresh;
   V* const basis = run == 0 ? (V*)a.basis : nullptr;
 
-  // PIPE: one row's gathers (up hops, down hops, own entry)
-  double gu[PIPE ? E : 1], gd[PIPE ? E : 1], go = 0.0;
-  auto gather = [&](int r, double* hu, double* hd, double& ho) {
+  // PIPE: one row's gathers (down hops, up hops), issued in reverse order of
+  // use: LDS returns in order, so the row's first FMA waits for the row's last
+  // read and one counted wait covers the row (the own entry is in u[r])
+  double gu[PIPE ? E : 1], gd[PIPE ? E : 1];
+  auto gather = [&](int r, double* hu, double* hd) {
     if constexpr (PIPE) {
 #pragma unroll
-      for (int e = 0; e < E; e++) hu[e] = lds_ldv<double>(ucol[e] + r * VSLOT * 8);  // slot r of row iw
+      for (int e = E - 1; e >= 0; e--) hd[e] = lds_ldv<double>(dcol[r * E + e]);
 #pragma unroll
-      for (int e = 0; e < E; e++) hd[e] = lds_ldv<double>(dcol[r * E + e]);
-      if constexpr (UREG) ho = u[r];
-      else ho = vl[LPOS(r)];
+      for (int e = E - 1; e >= 0; e--) hu[e] = lds_ldv<double>(ucol[e] + r * VSLOT * 8);  // slot r of row iw
     }
   };
-  gather(0, gu, gd, go);
+  gather(0, gu, gd);
 
   for (int k = 0; k < a.niter; k++) {
     const int it = it0 + k;
@@ -521,23 +524,31 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
     // step (one integer op) instead of being hoisted into 1-2 VGPRs per row
     asm volatile("" : "+v"(q.row0));
     // ---- w = (H r_k)/b_k - b_k p ; alpha partial
-    V w[RPT];
+    // (PIPE: w[r] is written into u[r], whose old value row r has just used)
+    V wl[PIPE ? 1 : RPT];
+    V* const w = PIPE ? u : wl;
     double ap = 0.0;
     if constexpr (PIPE) {
       // MODE 4: software-pipelined gathers — row r+1's 2E LDS reads are in
       // flight while row r is summed (issued per hop group of 4 and waited
       // at once, one wave had <= 4 reads outstanding: the LDS latency was
       // exposed ~20 times per step at 2 waves per SIMD); row 0's reads were
-      // issued behind the previous step's beta barrier.
+      // issued behind the previous step's beta barrier.  The fence behind
+      // the gather keeps row r + 1's reads together ahead of row r's FMAs:
+      // one s_waitcnt lgkmcnt(2E) per row (left alone the scheduler
+      // interleaves two rows with a counted wait before almost every FMA).
       // (A rolling window of 12-16 reads per wave from asm statements with
       // counted waits, lgkmcnt(0) on the last rows only, measured slower: a
       // wait, a pad and a read per FMA cost more issue slots than the
       // latency they hide; profiles/persist_mode4/INDEX.md.)
 #pragma unroll
       for (int r = 0; r < RPT; r++) {
-        double nu[E], nd[E], no = 0.0;
-        if (r + 1 < RPT) gather(r + 1, nu, nd, no);
-        const double ur = go;
+        double nu[E], nd[E];
+        if (r + 1 < RPT) {
+          gather(r + 1, nu, nd);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        const double ur = u[r];
         double acc = ur * dgr[r];
 #ifndef ED_P4_NOGATHER  // timing probe: the step without its gathers
 #pragma unroll
@@ -563,7 +574,6 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
             gu[e] = nu[e];
             gd[e] = nd[e];
           }
-          go = no;
         }
       }
     } else {
@@ -697,7 +707,7 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
       // r_{k+1} is published: the next step's first row of gathers goes out
       // ahead of the square root and the reciprocal (~30 dependent f64
       // instructions that need no LDS)
-      gather(0, gu, gd, go);
+      gather(0, gu, gd);
       __builtin_amdgcn_sched_barrier(0);
     }
 #ifdef ED_P4_NOBETA
