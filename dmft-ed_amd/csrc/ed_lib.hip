@@ -32,6 +32,7 @@
 #include "ed_host.hpp"
 #include "ed_hosteig.hpp"
 #include "ed_obs.hpp"
+#include "ed_twin.hpp"
 
 using namespace edg;
 
@@ -3606,7 +3607,7 @@ static constexpr int32_t kOptKnown =
     ED_OPT_NO_PERSIST | ED_OPT_PERSIST_STORED | ED_OPT_NO_PREG | ED_OPT_NO_PKRON | ED_OPT_SPLIT_SIMPLE |
     ED_OPT_NO_BATCH | ED_OPT_EIGH_NO_VERIFY | ED_OPT_TRLAN_UNFUSED | ED_OPT_TRLAN_NOFOLD | ED_OPT_NO_GRAPH |
     ED_OPT_TRLAN_NOLOCAL | ED_OPT_TRLAN_NOSOLO | ED_OPT_TRLAN_FULLUPD | ED_OPT_STORED_EXACT |
-    ED_OPT_EIGH_FULLPROBE | ED_OPT_NO_FUSED | ED_OPT_EIGH_NOHINT;
+    ED_OPT_EIGH_FULLPROBE | ED_OPT_NO_FUSED | ED_OPT_EIGH_NOHINT | ED_OPT_TWIN_GATHER;
 
 int ed_sector_set_options(ed_sector* s, int32_t opts) {
   if (!s) return fail(ED_ERR_ARG, "null");
@@ -4059,6 +4060,66 @@ int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t o
     hipLaunchKernelGGL(k_apply_op_acc<false>, dim3(grid_for(src->dim)), dim3(kBlock), 0, st,
                        src->d_map, src->dim, idx, op, level, coef_re, coef_im,
                        (const double*)src_vec, (double*)dst_vec);
+  HIPCK(hipGetLastError());
+  return ED_OK;
+}
+
+// ------------------------------------------------ twin-sector vectors
+// (ed_twin.hpp).  get_twin_sector (ED_SETUP.f90:1196-1212): (nup, ndw) ->
+// (ndw, nup), sz -> -sz, n -> 2*Ns - n; it knows no (n, twoJz) sectors.
+static int check_twin_pair(const ed_sector* src, const ed_sector* dst) {
+  if (!src || !dst) return fail(ED_ERR_ARG, "null");
+  if (src->device != dst->device) return fail(ED_ERR_ARG, "sectors on different devices");
+  const EdModel &a = src->Mh, &b = dst->Mh;
+  if (a.ns != b.ns || a.norb != b.norb || a.nbath != b.nbath || a.nspin != b.nspin || a.mode != b.mode ||
+      a.bath != b.bath || a.jz != b.jz)
+    return fail(ED_ERR_ARG, "sectors of different models");
+  if (a.jz) return fail(ED_ERR_ARG, "twin sectors are not defined in the Jz basis");
+  int e1, e2 = 0;
+  if (a.mode == ED_MODE_NORMAL) {
+    e1 = src->T.q2;
+    e2 = src->T.q1;
+  } else if (a.mode == ED_MODE_SUPERC) {
+    e1 = -src->T.q1;
+  } else {
+    e1 = 2 * a.ns - src->T.q1;
+  }
+  if (dst->T.q1 != e1 || (a.mode == ED_MODE_NORMAL && dst->T.q2 != e2) || dst->dim != src->dim)
+    return fail(ED_ERR_ARG, "dst is not the twin sector of src");
+  return ED_OK;
+}
+
+int ed_sector_twin_vector(const ed_sector* src, const ed_sector* dst, int32_t vtype, const void* src_vec,
+                          void* dst_vec, void* stream) {
+  if (!src_vec || !dst_vec || src_vec == dst_vec) return fail(ED_ERR_ARG, "null or aliased vectors");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  CK(check_twin_pair(src, dst));
+  CK(whole_only(src));
+  CK(whole_only(dst));
+  HIPCK(hipSetDevice(src->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t dim = dst->dim;
+  if (src->Mh.mode == ED_MODE_NORMAL && !(dst->opts & ED_OPT_TWIN_GATHER)) {
+    const int64_t R = src->T.dimdw, C = src->T.dimup;  // the partner's view: idw rows, iup fast
+    const int64_t nt = ((R + kTwinTile - 1) / kTwinTile) * ((C + kTwinTile - 1) / kTwinTile);
+    const int g = (int)std::min<int64_t>(nt, 8 * 256);
+    if (vtype)
+      hipLaunchKernelGGL(k_twin_transpose<true>, dim3(g), dim3(kBlock), 0, st, R, C, (const double2*)src_vec,
+                         (double2*)dst_vec);
+    else
+      hipLaunchKernelGGL(k_twin_transpose<false>, dim3(g), dim3(kBlock), 0, st, R, C, (const double*)src_vec,
+                         (double*)dst_vec);
+  } else {
+    const DevIndex idx{src->d_off, src->d_rank, src->T.ns, src->T.nst - 1};
+    const int nb = 2 * src->Mh.ns;
+    const uint32_t full = nb >= 32 ? 0xFFFFFFFFu : (1u << nb) - 1u;
+    if (vtype)
+      hipLaunchKernelGGL(k_twin_gather<true>, dim3(grid_for(dim)), dim3(kBlock), 0, st, dst->d_map, dim, idx,
+                         src->Mh.mode, full, (const double2*)src_vec, (double2*)dst_vec);
+    else
+      hipLaunchKernelGGL(k_twin_gather<false>, dim3(grid_for(dim)), dim3(kBlock), 0, st, dst->d_map, dim, idx,
+                         src->Mh.mode, full, (const double*)src_vec, (double*)dst_vec);
+  }
   HIPCK(hipGetLastError());
   return ED_OK;
 }

@@ -25,6 +25,7 @@ OPTIONS = {
     "trlan_unfused": 0x100, "trlan_nofold": 0x200, "no_graph": 0x800,
     "trlan_nolocal": 0x1000, "trlan_nosolo": 0x2000, "trlan_fullupd": 0x4000,
     "stored_exact": 0x100000, "eigh_fullprobe": 0x200000, "no_fused": 0x400000, "eigh_nohint": 0x800000,
+    "twin_gather": 0x1000000,
 }
 ED_OK = 0
 ERRORS = {1: "ED_ERR_ARG", 2: "ED_ERR_STATE", 3: "ED_ERR_HIP", 4: "ED_ERR_OOM",
@@ -57,6 +58,7 @@ SIGNATURES = {
     "ed_sector_sell_view": ([_P, _P], ctypes.c_int),
     "ed_sector_apply_op": ([_P, _P, _i32, _i32, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_apply_op_acc": ([_P, _P, _i32, _i32, _f64, _f64, _i32, _P, _P, _P], ctypes.c_int),
+    "ed_sector_twin_vector": ([_P, _P, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_nn_moments": ([_P, _i32, _P, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_expect": ([_P, _i32, _P, _i32, _P, _P, _P, _P, _P], ctypes.c_int),
     "ed_sector_lanc_tridiag_dev": ([_P, _i32, _P, _i32, _f64, _P, _P, _P], ctypes.c_int),

@@ -13,6 +13,16 @@ The T=0 state list follows :217-236 (gs_threshold window, 10*gs_threshold
 reset).  Sectors can be restricted (the farm hands each rank its subset);
 `state_list` replays the list logic in isector order over gathered
 eigenvalues, so a farmed run reproduces the serial list exactly.
+
+Finite temperature (lanc_nstates_total > 1, ED_SETUP.f90:261-283): the list is
+the reference's size-capped, energy-ordered one (es_add_state / es_pop_state,
+ED_EIGENSPACE.f90:138-218, :231-295), every consumer weights a state by
+exp(-beta (E - Egs)) / Z, and `post_diag` (ED_DIAG.f90:494-565) trims the list
+at `cutoff` and adapts neigen_sector and lanc_nstates_total for the next
+iteration.  With ed_twin only one sector of every twin pair is diagonalised
+(sectors.diag_sectors); its states enter the list followed by a twin entry
+without a vector, which `state_vector` rebuilds on the device on demand
+(Sector.twin_vector) and never stores.
 """
 from __future__ import annotations
 
@@ -24,7 +34,7 @@ import numpy as np
 from .hamiltonian import Sector
 from .params import EDConfig
 from .sectors import Sector as SectorId
-from .sectors import diag_sectors
+from .sectors import diag_sectors, has_twin, setup_pointers, twin_sector
 
 
 @dataclass
@@ -90,6 +100,36 @@ class DiagOptions:
     # key-value store, so the ranks finish together whatever the cost
     # model's error; "lpt" — the static longest-processing-time partition
     farm_schedule: str = "dynamic"
+    # finite temperature (ED_INPUT_VARS.f90:167-169, beta :129, cutoff :162,
+    # ed_twin :136): lanc_nstates_total == 1 is the T=0 calculation
+    # (ED_SETUP.f90:261-266); otherwise the state list holds up to
+    # lanc_nstates_total states weighted exp(-beta (E - Egs)), and post_diag
+    # trims it where that weight falls to `cutoff` and moves
+    # lanc_nstates_total by lanc_nstates_step
+    lanc_nstates_total: int = 1
+    lanc_nstates_step: int = 2
+    beta: float = 1000.0
+    cutoff: float = 1e-9
+    # diagonalise one sector of every twin pair only (nup >= ndw; superc
+    # sz <= 0; nonsu2 n <= Ns) and list the other one's states as twin
+    # entries.  Nothing checks that the model has the symmetry (spin exchange;
+    # particle-hole in nonsu2): the reference assumes it, and so does this
+    ed_twin: bool = False
+    # isector -> eigenpairs wanted from that sector (post_diag's adaptive
+    # neigen_sector, ED_DIAG.f90:503-515); None / absent: lanc_nstates_sector
+    neigen_sector: Optional[Dict[int, int]] = None
+
+    def __post_init__(self):
+        # ED_SETUP.f90:270-278: at finite T both counts are made even when the
+        # options are set up (doublets are kept whole); post_diag's later
+        # values of lanc_nstates_total are used as they come, as there
+        if self.finite_t:
+            self.lanc_nstates_sector += self.lanc_nstates_sector % 2
+            self.lanc_nstates_total += self.lanc_nstates_total % 2
+
+    @property
+    def finite_t(self) -> bool:
+        return self.lanc_nstates_total != 1
 
 
 @dataclass
@@ -105,11 +145,22 @@ class SectorResult:
 
 @dataclass
 class StateList:
-    """state_list at T=0: energies, sectors and (optionally) vectors."""
+    """state_list: energies, sectors and (optionally) vectors of the kept
+    states.  twin_of[k] is the index of the entry that holds the vector of a
+    twin entry k (None for an ordinary entry): a twin entry reports its
+    partner's energy and the twin sector's isector, and vectors[k] is None
+    (`state_vector` rebuilds it).  finite_t / beta: the weights' temperature."""
 
     energies: List[float] = field(default_factory=list)
     sectors: List[int] = field(default_factory=list)
     vectors: List[Optional[np.ndarray]] = field(default_factory=list)
+    twin_of: Optional[List[Optional[int]]] = None
+    finite_t: bool = False
+    beta: float = 1000.0
+
+    def __post_init__(self):
+        if self.twin_of is None:
+            self.twin_of = [None] * len(self.energies)
 
     @property
     def emin(self) -> float:
@@ -119,11 +170,35 @@ class StateList:
     def size(self) -> int:
         return len(self.energies)
 
+    def partner(self, k: int) -> Optional[int]:
+        return self.twin_of[k] if k < len(self.twin_of) else None
 
-def lanczos_params(dim: int, opt: DiagOptions) -> Tuple[int, int, int]:
-    """(Neigen, Nitermax, Nblock), ED_DIAG.f90:88-97 (neigen_sector from
-    setup_pointers: min(dim, lanc_nstates_sector))."""
+    def weights(self) -> np.ndarray:
+        """exp(-beta (E - Egs)) per entry at finite T (ED_DIAG.f90:405-409),
+        1.0 each at T=0 (zeta_function = state_list%size, :411)."""
+        e = np.asarray(self.energies, dtype=np.float64)
+        if not self.finite_t:
+            return np.ones(len(e))
+        return np.exp(-self.beta * (e - self.emin))
+
+    @property
+    def zeta(self) -> float:
+        return float(np.sum(self.weights()))
+
+    def with_vectors(self, vectors) -> "StateList":
+        """The same list with other vector objects (copies, broadcasts)."""
+        return StateList(list(self.energies), list(self.sectors), list(vectors), list(self.twin_of),
+                         self.finite_t, self.beta)
+
+
+def lanczos_params(dim: int, opt: DiagOptions, isector: Optional[int] = None) -> Tuple[int, int, int]:
+    """(Neigen, Nitermax, Nblock), ED_DIAG.f90:88-97; neigen_sector(isector)
+    from opt.neigen_sector where it has the sector (post_diag's adapted
+    values), else setup_pointers' min(dim, lanc_nstates_sector)
+    (ED_SETUP.f90:427-429)."""
     neigen_sector = min(dim, opt.lanc_nstates_sector)
+    if opt.neigen_sector is not None and isector is not None and isector in opt.neigen_sector:
+        neigen_sector = int(opt.neigen_sector[isector])
     if opt.lanc_method == "lanczos":
         return 1, min(dim, opt.lanc_niter), 1
     neigen = min(dim, neigen_sector)
@@ -178,7 +253,7 @@ def _worker_stream(opt: DiagOptions, device: int):
 def solve_sector(cfg: EDConfig, sec: SectorId, opt: DiagOptions, device: int = 0) -> SectorResult:
     dim = sec.dim
     st = _worker_stream(opt, device)
-    neigen, nitermax, nblock = lanczos_params(dim, opt)
+    neigen, nitermax, nblock = lanczos_params(dim, opt, sec.isector)
     lanc_solve = not (neigen == dim or dim <= max(opt.lanc_dim_threshold, opt.mpi_size))
     real = cfg.is_real()
     q = (sec.q1, sec.q2)
@@ -220,7 +295,7 @@ def batchable(cfg: EDConfig, sec: SectorId, opt: DiagOptions) -> bool:
     at most opt.batch_max_dim rows, a Krylov basis of at most 32 columns."""
     if opt.batch_max_dim <= 0 or opt.lanc_method != "arpack" or not cfg.is_real():
         return False
-    neigen, _, nblock = lanczos_params(sec.dim, opt)
+    neigen, _, nblock = lanczos_params(sec.dim, opt, sec.isector)
     if neigen == sec.dim or sec.dim <= max(opt.lanc_dim_threshold, opt.mpi_size):
         return False
     ncv = min(max(nblock, neigen + 1), 64, sec.dim)
@@ -236,7 +311,7 @@ def solve_batch(cfg: EDConfig, secs: List[SectorId], opt: DiagOptions, device: i
     st = _worker_stream(opt, device)
     groups: Dict[Tuple[int, int], List[int]] = {}
     for k, sec in enumerate(secs):
-        neigen, nitermax, nblock = lanczos_params(sec.dim, opt)
+        neigen, nitermax, nblock = lanczos_params(sec.dim, opt, sec.isector)
         ncv = min(max(nblock, neigen + 1), 64, sec.dim)
         groups.setdefault((neigen, ncv), []).append(k)
     out: List[Optional[SectorResult]] = [None] * len(secs)
@@ -250,7 +325,7 @@ def solve_batch(cfg: EDConfig, secs: List[SectorId], opt: DiagOptions, device: i
     # opt.workers threads, then one batch call, then the frees in parallel
     with ThreadPoolExecutor(max_workers=max(1, opt.workers)) as ex:
         for (neigen, ncv), ks in groups.items():
-            maxit = [max(lanczos_params(secs[k].dim, opt)[1], 10) for k in ks]
+            maxit = [max(lanczos_params(secs[k].dim, opt, secs[k].isector)[1], 10) for k in ks]
             futs = [ex.submit(build, k) for k in ks]
             hs: List[Sector] = []
             try:
@@ -278,22 +353,126 @@ def solve_batch(cfg: EDConfig, secs: List[SectorId], opt: DiagOptions, device: i
     return out
 
 
-def state_list(results: Iterable[SectorResult], opt: DiagOptions) -> StateList:
-    """T=0 state list, ED_DIAG.f90:224-235, replayed in isector order."""
-    sl = StateList()
+def _twin_isector(cfg: Optional[EDConfig], r: SectorResult, opt: DiagOptions) -> Optional[int]:
+    """isector of the twin entry that sector r's states bring (Tflag,
+    ED_DIAG.f90:76-84), None if they bring none."""
+    if not opt.ed_twin:
+        return None
+    if cfg is None:
+        raise ValueError("state_list: ed_twin needs the configuration (the twin sectors' isector)")
+    sec = setup_pointers(cfg)[r.isector - 1]
+    return twin_sector(cfg, sec).isector if has_twin(cfg, sec) else None
+
+
+def _pop_state(rows: list) -> None:
+    """es_pop_state of the last entry (ED_EIGENSPACE.f90:231-295): a twin
+    entry goes together with the vector entry in front of it."""
+    n = 2 if rows[-1][3] else 1
+    del rows[-n:]
+
+
+def _from_rows(rows: list, finite_t: bool, beta: float) -> StateList:
+    return StateList([r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows],
+                     [k - 1 if r[3] else None for k, r in enumerate(rows)], finite_t, beta)
+
+
+def state_list(results: Iterable[SectorResult], opt: DiagOptions, cfg: Optional[EDConfig] = None) -> StateList:
+    """The state list of ed_diag_c (ED_DIAG.f90:220-236), replayed in isector
+    order.  T=0: the gs_threshold window (:224-235).  Finite T: every state
+    through es_add_state(..., twin=Tflag, size=lanc_nstates_total)
+    (ED_EIGENSPACE.f90:138-218): the list is ordered by energy, a new entry
+    goes in front of entries of equal energy (e <= c%e), a full list takes a
+    state only below its last energy after one es_pop_state, and a state of a
+    sector with a twin (`cfg` needed) enters as [vector entry, twin entry],
+    never split — so a pop may remove two and the size may pass the cap by one."""
+    rows: list = []          # (energy, isector, vector, is twin entry)
     oldzero = 1000.0
+    cap = opt.lanc_nstates_total
     for r in sorted(results, key=lambda r: r.isector):
+        tw = _twin_isector(cfg, r, opt)
         for i in range(r.neigen):
             enemin = float(r.eigenvalues[i])
             vec = r.vectors[:, i] if r.vectors is not None else None
-            if enemin < oldzero - 10.0 * opt.gs_threshold:
+            new = [(enemin, r.isector, vec, False)] + ([(enemin, tw, None, True)] if tw is not None else [])
+            if opt.finite_t:
+                if len(rows) >= cap:
+                    if not enemin < rows[-1][0]:
+                        continue
+                    _pop_state(rows)
+                at = next((k for k, c in enumerate(rows) if enemin <= c[0]), len(rows))
+                rows[at:at] = new
+            elif enemin < oldzero - 10.0 * opt.gs_threshold:
                 oldzero = enemin
-                sl = StateList()
-                sl.energies.append(enemin); sl.sectors.append(r.isector); sl.vectors.append(vec)
+                rows = list(new)
             elif abs(enemin - oldzero) <= opt.gs_threshold:
                 oldzero = min(oldzero, enemin)
-                sl.energies.append(enemin); sl.sectors.append(r.isector); sl.vectors.append(vec)
-    return sl
+                rows.extend(new)
+    return _from_rows(rows, opt.finite_t, opt.beta)
+
+
+def post_diag(states: StateList, opt: DiagOptions, cfg: Optional[EDConfig] = None) -> Tuple[StateList, DiagOptions]:
+    """The data part of ed_post_diag at finite T (ED_DIAG.f90:494-565; the
+    files stay out): returns the trimmed list and the options of the next
+    diagonalisation.  neigen_sector: +1 for a sector present in the list, -1
+    otherwise, at most its count in the list + 1 and at least 1 (:503-515) —
+    for every sector of `cfg` when given, else for the sectors opt.neigen_sector
+    or the list name.  If the last state still weighs more than `cutoff`,
+    lanc_nstates_total grows by lanc_nstates_step (:525-527); otherwise the
+    states of weight <= cutoff are popped from the end, twin pairs together,
+    and lanc_nstates_total = max(size, step) + step (:533-562).  T=0: the inputs."""
+    if not states.finite_t or states.size == 0:
+        return states, opt
+    count: Dict[int, int] = {}
+    for isec in states.sectors:
+        count[isec] = count.get(isec, 0) + 1
+    old = dict(opt.neigen_sector or {})
+    if cfg is not None:
+        known = {s.isector: s.dim for s in setup_pointers(cfg)}
+    else:
+        known = {i: None for i in set(old) | set(count)}
+    neig: Dict[int, int] = {}
+    for i, dim in known.items():
+        base = opt.lanc_nstates_sector if dim is None else min(dim, opt.lanc_nstates_sector)
+        n = int(old.get(i, base)) + (1 if i in count else -1)
+        if n > count.get(i, 0):
+            n = count.get(i, 0) + 1
+        neig[i] = max(n, 1)
+    rows = [(e, i, v, t is not None) for e, i, v, t in
+            zip(states.energies, states.sectors, states.vectors, states.twin_of)]
+    egs = states.emin
+    total = opt.lanc_nstates_total
+    if np.exp(-states.beta * (rows[-1][0] - egs)) > opt.cutoff:
+        total += opt.lanc_nstates_step
+    else:
+        while np.exp(-states.beta * (rows[-1][0] - egs)) <= opt.cutoff:
+            _pop_state(rows)
+        total = max(len(rows), opt.lanc_nstates_step) + opt.lanc_nstates_step
+    nopt = replace(opt, neigen_sector=neig)
+    nopt.lanc_nstates_total = total      # as it comes: only the set-up makes it even
+    return _from_rows(rows, True, states.beta), nopt
+
+
+def state_vector(cfg: EDConfig, states: StateList, k: int, device: int = 0, sector_of=None):
+    """Vector of kept state k: vectors[k] of an ordinary entry; for a twin
+    entry the partner's vector reordered into the twin sector on the device
+    (Sector.twin_vector; es_return_cvector, ED_EIGENSPACE.f90:414-445).  The
+    twin vector is built per call and not stored, as in the reference, so the
+    list keeps holding the kept states' vectors only.  sector_of(sec): a
+    caller's cache of device sectors (the basis is all that is used);
+    without one the two sectors are built and freed here."""
+    p = states.partner(k)
+    if p is None:
+        return states.vectors[k]
+    vec = states.vectors[p]
+    if vec is None:
+        return None
+    secs = setup_pointers(cfg)
+    src, dst = secs[states.sectors[p] - 1], secs[states.sectors[k] - 1]
+    if sector_of is not None:
+        return sector_of(src).twin_vector(sector_of(dst), vec)
+    mk = lambda s: Sector(cfg, s.q1, s.q2, stored=False, direct=True, real=cfg.is_real(), device=device)  # noqa: E731
+    with mk(src) as A, mk(dst) as B:
+        return A.twin_vector(B, vec)
 
 
 def retain_state_vectors(sl: StateList, results: Iterable[SectorResult],
@@ -304,19 +483,18 @@ def retain_state_vectors(sl: StateList, results: Iterable[SectorResult],
     HBM held after the diagonalisation is the kept states alone.  Host (numpy)
     blocks are never dropped."""
     vecs = [v.clone() if (v is not None and not isinstance(v, np.ndarray)) else v for v in sl.vectors]
-    if not drop_blocks:
-        return StateList(list(sl.energies), list(sl.sectors), vecs)
-    for r in results:
-        if r.vectors is not None and not isinstance(r.vectors, np.ndarray):
-            r.vectors = None
-    return StateList(list(sl.energies), list(sl.sectors), vecs)
+    if drop_blocks:
+        for r in results:
+            if r.vectors is not None and not isinstance(r.vectors, np.ndarray):
+                r.vectors = None
+    return sl.with_vectors(vecs)
 
 
 def working_set_bytes(cfg: EDConfig, sec: SectorId, opt: DiagOptions) -> float:
     """Device bytes a sector's solve streams repeatedly: the Krylov basis
     (Nblock columns), the packed stored H (4 B per element, ~1 + Norb*Nbath
     per row) and the O(dim) vectors (diagonal, residual, scratch)."""
-    _, _, nblock = lanczos_params(sec.dim, opt)
+    _, _, nblock = lanczos_params(sec.dim, opt, sec.isector)
     vs = 8 if cfg.is_real() else 16
     return float(sec.dim) * (nblock * vs + 4.0 * (1 + cfg.Norb * cfg.Nbath) + 4 * vs)
 
@@ -475,11 +653,11 @@ def ed_diag(cfg: EDConfig, opt: Optional[DiagOptions] = None,
             sectors: Optional[Iterable[int]] = None, device: int = 0):
     """Diagonalise all (or the given) sectors; returns (results, state_list)."""
     opt = opt or DiagOptions()
-    secs = diag_sectors(cfg)
+    secs = diag_sectors(cfg, opt.ed_twin)
     pick = set(sectors) if sectors is not None else None
     todo = [sec for sec in secs if pick is None or sec.isector in pick]
     results = solve_many(cfg, todo, opt, device)
-    return results, retain_state_vectors(state_list(results, opt), results, drop_blocks=not opt.retain_all)
+    return results, retain_state_vectors(state_list(results, opt, cfg), results, drop_blocks=not opt.retain_all)
 
 
 def eigenvalues_table(results: Iterable[SectorResult]) -> Dict[int, np.ndarray]:

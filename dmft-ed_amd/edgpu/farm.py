@@ -61,7 +61,7 @@ def sector_cost(cfg: EDConfig, sec: SectorId, opt: DiagOptions) -> float:
     11.2 ms + 1.34e-11): small Lanczos sectors are dominated by the fixed
     part, which a purely proportional model gave to the ranks holding many
     of them.  Only ratios matter (LPT, and the dynamic schedule's order)."""
-    neigen, nitermax, _ = lanczos_params(sec.dim, opt)
+    neigen, nitermax, _ = lanczos_params(sec.dim, opt, sec.isector)
     if neigen == sec.dim or sec.dim <= max(opt.lanc_dim_threshold, opt.mpi_size):
         return 2e-3 + float(sec.dim) ** 3 * 1e-10
     per_row = 1.0 + cfg.Norb * cfg.Nbath
@@ -108,7 +108,7 @@ def farm_diag(cfg: EDConfig, opt: Optional[DiagOptions] = None, *, device: int =
     dist = _dist()
     rank = dist.get_rank() if dist else 0
     world = dist.get_world_size() if dist else 1
-    secs = [s for s in diag_sectors(cfg) if sectors is None or s.isector in set(sectors)]
+    secs = [s for s in diag_sectors(cfg, opt.ed_twin) if sectors is None or s.isector in set(sectors)]
     local: Dict[int, SectorResult] = {}
     dynamic = bool(dist and world > 1 and opt.farm_schedule == "dynamic")
     # dynamic queue: the small sectors solve_batch takes are dealt to the
@@ -173,8 +173,11 @@ def farm_diag(cfg: EDConfig, opt: Optional[DiagOptions] = None, *, device: int =
     for k, (q, dim, neigen, ev) in merged.items():
         loc = local.get(k)
         shadows.append(SectorResult(k, q, dim, ev, neigen, loc.vectors if loc is not None else None))
-    states = retain_state_vectors(state_list(shadows, opt), list(local.values()), drop_blocks=not opt.retain_all)
-    owners = [owner_of[s] for s in states.sectors]
+    states = retain_state_vectors(state_list(shadows, opt, cfg), list(local.values()),
+                                  drop_blocks=not opt.retain_all)
+    # a twin entry names a sector no rank solved: its vector is rebuilt from its partner's
+    owners = [owner_of[states.sectors[k if states.partner(k) is None else states.partner(k)]]
+              for k in range(states.size)]
     tables = {k: v[3] for k, v in merged.items()}
     return FarmResult(states, owners, tables, local, assignment)
 

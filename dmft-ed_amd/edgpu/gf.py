@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .diag import StateList, is_complex_vector
+from .diag import StateList, is_complex_vector, state_vector
 from .hamiltonian import Sector
 from .params import EDConfig
 from .sectors import c_sector, cdg_sector, setup_pointers
@@ -275,10 +275,28 @@ def _job_list(cfg: EDConfig, states: StateList):
     return jobs, pairs
 
 
+def _peso_bz(states: StateList, k: int, weight, norm2: float, zeta: float):
+    """pesoBZ of add_to_lanczos_gf_normal (ED_GF_NORMAL.f90:596-601) times the
+    seed's weight: norm2 / zeta at T=0; at finite T norm2 exp(-beta (Ei - Egs))
+    / zeta, and 0 once beta (Ei - Egs) reaches 200."""
+    if not states.finite_t:
+        return weight * norm2 / zeta
+    x = states.beta * (states.energies[k] - states.emin)
+    if not x < 200.0:
+        return 0.0
+    return weight * (norm2 * np.exp(-x) / zeta)
+
+
+def _state_vec(cfg, states, k, cache):
+    """Kept state k's vector; a twin entry's is rebuilt on the device from its
+    partner's with the cache's (matrix-free) sector handles."""
+    return state_vector(cfg, states, k, cache.device, lambda s: cache.get(s, False))
+
+
 def _run_job(cfg, states, gopt, job, cache, poles, record, zeta):
     """One tridiagonalisation; its poles are queued on `poles` (PoleSums)."""
     comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = job
-    e_i, vec = states.energies[k], states.vectors[k]
+    e_i, vec = states.energies[k], _state_vec(cfg, states, k, cache)
     if vec is None:
         raise ValueError("the Green's function needs the state vectors (keep_vectors=True)")
     cplx = (not cfg.is_real()) or is_complex_vector(vec) or any(np.imag(c) != 0 for _, c in terms)
@@ -293,7 +311,7 @@ def _run_job(cfg, states, gopt, job, cache, poles, record, zeta):
     if record is not None:
         record.append(dict(channel=tag, isector=states.sectors[k], op=op, norm2=norm2, alfa=a, beta=b,
                            nlanc=n))
-    poles.add(comp, weight * norm2 / zeta, e_i, E, z, isign)
+    poles.add(comp, _peso_bz(states, k, weight, norm2, zeta), e_i, E, z, isign)
 
 
 def _tridiag_batch(S: Sector, seeds, nlanc: int, real: bool, threshold: float):
@@ -323,7 +341,8 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
     groups = {}
     for n in todo:
         comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
-        vec = states.vectors[k]
+        p = states.partner(k)
+        vec = states.vectors[k if p is None else p]    # a twin's vector has its partner's type
         if vec is None:
             raise ValueError("the Green's function needs the state vectors (keep_vectors=True)")
         cplx = (not cfg.is_real()) or is_complex_vector(vec) or any(np.imag(c) != 0 for _, c in terms)
@@ -335,7 +354,7 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
             for n in members:
                 comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
                 HI, HJ = cache.get(sec, False), cache.get(jsec, True)
-                seed, norm2 = _seed(HI, HJ, op, terms, states.vectors[k], cplx)
+                seed, norm2 = _seed(HI, HJ, op, terms, _state_vec(cfg, states, k, cache), cplx)
                 if norm2 == 0.0:
                     continue
                 live.append(n)
@@ -356,7 +375,7 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
                 if record is not None:
                     record.append((n, dict(channel=tag, isector=states.sectors[k], op=op, norm2=norms[q],
                                            alfa=a[q], beta=b[q], nlanc=int(nl[q]))))
-                fracs[n] = (comp, weight * norms[q] / zeta, states.energies[k], E, z, isign)
+                fracs[n] = (comp, _peso_bz(states, k, weight, norms[q], zeta), states.energies[k], E, z, isign)
     finally:
         cache.close()
     for n in todo:
@@ -430,7 +449,10 @@ def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None,
     sums its poles into its own G, and one all_reduce adds the G arrays
     (2 x L complex numbers per component — no collective inside a job).  State
     vectors missing on a rank (farm_diag keeps them on their owner) are
-    broadcast from `owners` first.  `runner(cfg, states, gopt, job, wm, wr,
+    broadcast from `owners` first.  A finite-temperature list (states.finite_t)
+    weights every state by exp(-beta (Ei - Egs)) / zeta (ED_GF_NORMAL.f90:596-601)
+    and needs gopt.beta == states.beta; twin entries take their vector from
+    `state_vector`.  `runner(cfg, states, gopt, job, wm, wr,
     G_m, G_r, zeta)` replaces the device job (the CPU tests pass the oracle's)."""
     gopt = gopt or GFOptions()
     if cfg.ed_mode == "superc":
@@ -448,12 +470,14 @@ def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None,
 
         vecs = list(states.vectors)
         for k, isec in enumerate(states.sectors):
+            if states.partner(k) is not None:     # a twin entry: every rank rebuilds it from the partner
+                continue
             dim = setup_pointers(cfg)[isec - 1].dim
             cplx = not cfg.is_real() or is_complex_vector(vecs[k])
             flag = [cplx]
             dist.broadcast_object_list(flag, src=owners[k])
             vecs[k] = broadcast_vector(vecs[k], owners[k], dim, flag[0], device)
-        states = StateList(list(states.energies), list(states.sectors), vecs)
+        states = states.with_vectors(vecs)
     jobs, pairs = _job_list(cfg, states)
     if world > 1:
         from .farm import lpt_partition
@@ -462,7 +486,11 @@ def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None,
         mine = set(lpt_partition(costs, world)[rank])
     else:
         mine = set(range(len(jobs)))
-    zeta = float(states.size)       # T=0: zeta_function = state_list%size (ED_DIAG.f90:411)
+    if states.finite_t and gopt.beta != states.beta:
+        raise ValueError(f"build_gf: GFOptions.beta = {gopt.beta} but the state list was weighted at "
+                         f"beta = {states.beta}")
+    # zeta_function (ED_DIAG.f90:403-412): sum of exp(-beta (Ei - Egs)), state_list%size at T=0
+    zeta = states.zeta if states.finite_t else float(states.size)
     todo = [n for n in range(len(jobs)) if n in mine]
     poles = PoleSums(Nsp, No, wm, wr, gopt.eps, device) if runner is None else None
     if runner is None and gopt.batch:

@@ -98,7 +98,8 @@ class Sector:
         """Select kernel alternatives by name (ED_OPT_*: no_persist,
         persist_stored, no_preg, no_pkron, split_simple, no_batch,
         eigh_no_verify, trlan_unfused, trlan_nofold, no_graph, trlan_nolocal,
-        trlan_nosolo, trlan_fullupd, stored_exact, eigh_fullprobe, no_fused, eigh_nohint;
+        trlan_nosolo, trlan_fullupd, stored_exact, eigh_fullprobe, no_fused, eigh_nohint,
+        twin_gather;
         edgpu._lib.OPTIONS); no names
         restores the defaults."""
         bits = 0
@@ -307,6 +308,23 @@ class Sector:
         check(_lib.load().ed_sector_expect(self._h, vt, _tptr(x), len(terms), _ptr(nops), _ptr(lv), _ptr(op),
                                            _ptr(out), _stream_ptr(st)), "ed_sector_expect")
         return out[0::2] + 1j * out[1::2]
+
+    # ---------------------------------------------------------- twin sectors
+    def twin_vector(self, dst: "Sector", vec):
+        """The vector of a twin entry of the state list (es_return_cvector,
+        ED_EIGENSPACE.f90:414-445; ed_sector_twin_vector): `vec` lives in this
+        sector, `dst` is its twin sector (get_twin_sector, ED_SETUP.f90:1196-1212)
+        and the new device tensor t has t[i] = vec[row of flip_state(dst state i)]
+        = vec[argsort(flip_state(self.map()))][i], without sign or conjugation.
+        Normal mode runs the tiled transpose unless `dst` has the option
+        "twin_gather"."""
+        vt, x, st = self._state_arg(vec)
+        if dst.device != self.device:
+            raise ValueError("twin_vector: sectors on different devices")
+        out = self._out_array((dst.dim,), vt, True)
+        check(_lib.load().ed_sector_twin_vector(self._h, dst.handle, vt, _tptr(x), _tptr(out), _stream_ptr(st)),
+              "ed_sector_twin_vector")
+        return out
 
     def _out_array(self, shape, vt, on_device):
         if not on_device:

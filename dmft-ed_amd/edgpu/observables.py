@@ -33,7 +33,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .diag import StateList
+from .diag import StateList, state_vector
 from .hamiltonian import Sector
 from .params import EDConfig
 from .sectors import LZDIAG, setup_pointers
@@ -204,12 +204,15 @@ class _DeviceEvaluator:
     def __init__(self, device: int):
         self.device, self.cache = device, {}
 
-    def __call__(self, cfg, sec, vec, levels, terms):
+    def sector(self, cfg, sec) -> Sector:
         key = (sec.q1, sec.q2)
         if key not in self.cache:
             self.cache[key] = Sector(cfg, sec.q1, sec.q2, stored=False, direct=True, real=cfg.is_real(),
                                      device=self.device)
-        S = self.cache[key]
+        return self.cache[key]
+
+    def __call__(self, cfg, sec, vec, levels, terms):
+        S = self.sector(cfg, sec)
         if isinstance(vec, np.ndarray):      # a dense sector's host vector: one upload for both calls
             _, vec, _ = S._state_arg(vec)
         M, norm = S.nn_moments(vec, levels)
@@ -242,7 +245,12 @@ def _per_state(cfg: EDConfig, states: StateList, device: int, weights, owners, e
     rank = dist.get_rank() if dist else 0
     world = dist.get_world_size() if dist else 1
     n = states.size
-    w = np.full(n, 1.0 / n) if weights is None else np.asarray(weights, dtype=np.float64)
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64)
+    elif states.finite_t:           # peso / zeta_function (ED_OBSERVABLES.f90:119-120)
+        w = states.weights() / states.zeta
+    else:
+        w = np.full(n, 1.0 / n)
     if w.shape != (n,):
         raise ValueError("weights: one per kept state")
     levels = [imp_site(cfg, a, 0) for a in range(cfg.Norb)] + [imp_site(cfg, a, 1) for a in range(cfg.Norb)]
@@ -254,7 +262,8 @@ def _per_state(cfg: EDConfig, states: StateList, device: int, weights, owners, e
             mine = (owners[k] == rank) if (owners is not None and world > 1) else (k % world == rank)
             if not mine:
                 continue
-            vec = states.vectors[k]
+            sector_of = (lambda s: ev.sector(cfg, s)) if isinstance(ev, _DeviceEvaluator) else None
+            vec = state_vector(cfg, states, k, device, sector_of)
             if vec is None:
                 raise ValueError("the observables need the state vectors (keep_vectors=True; multi-rank: owners)")
             M, norm, vals = ev(cfg, secs[states.sectors[k] - 1], vec, levels, terms)
@@ -279,8 +288,10 @@ def observables(cfg: EDConfig, states: StateList, device: int = 0, weights: Opti
                 owners: Optional[List[int]] = None, evaluator=None) -> Observables:
     """observables_impurity (ED_OBSERVABLES.f90:48-715) from device-resident
     state vectors.  weights[k] is the Boltzmann factor of kept state k divided
-    by the partition function (peso/zeta_function, :119-120); default: the
-    T=0 value 1/states.size.
+    by the partition function (peso/zeta_function, :119-120); default:
+    states.weights() / states.zeta, which at T=0 is 1/states.size.  A twin
+    entry is evaluated from its partner's vector reordered on the device
+    (state_vector) by the rank that owns the partner.
 
     magx, magy (nonsu2): Re and Im of <c^+_{a up} c_{a dw}>.  The reference
     takes them from two seed norms (:234-337): expanding

@@ -125,14 +125,62 @@ def _setup_pointers(cfg: EDConfig) -> List[Sector]:
     return out
 
 
-def diag_sectors(cfg: EDConfig) -> List[Sector]:
+def twin_masked(cfg: EDConfig, sec: Sector) -> bool:
+    """.not.twin_mask(isector) with ed_twin: the sectors left to their twins
+    (nup < ndw ED_SETUP.f90:432-440, sz > 0 :553-560, n > Ns :713-722)."""
+    if cfg.ed_mode == "normal":
+        return sec.q1 < sec.q2
+    if cfg.ed_mode == "superc":
+        return sec.q1 > 0
+    return sec.q1 > cfg.Ns
+
+
+def has_twin(cfg: EDConfig, sec: Sector) -> bool:
+    """Tflag of a visited sector under ed_twin (ED_DIAG.f90:76-84): its states
+    enter the list with a twin entry unless the sector is its own twin."""
+    if cfg.ed_mode == "normal":
+        return sec.q1 != sec.q2
+    if cfg.ed_mode == "superc":
+        return sec.q1 != 0
+    return sec.q1 != cfg.Ns
+
+
+def twin_sector(cfg: EDConfig, sec: Sector) -> Sector:
+    """get_twin_sector (ED_SETUP.f90:1196-1212): (nup, ndw) -> (ndw, nup),
+    sz -> -sz, n -> 2*Ns - n.  Not defined in the Jz basis."""
+    if cfg.ed_mode == "nonsu2" and cfg.Jz_basis:
+        raise NotImplementedError("twin sectors in the Jz basis (get_twin_sector is not Jz-aware)")
+    if cfg.ed_mode == "normal":
+        q = (sec.q2, sec.q1)
+    elif cfg.ed_mode == "superc":
+        q = (-sec.q1, 0)
+    else:
+        q = (2 * cfg.Ns - sec.q1, 0)
+    return get_sector(cfg)[q]
+
+
+def diag_sectors(cfg: EDConfig, ed_twin: bool = False) -> List[Sector]:
     """The sectors ed_diag visits (ED_DIAG.f90:71-74): non-empty (Jz_basis
-    lists empty (n, twoJz) sectors), |twoJz| <= 2*Jz_max_value if Jz_max."""
+    lists empty (n, twoJz) sectors), |twoJz| <= 2*Jz_max_value if Jz_max, and
+    with ed_twin only one of every twin pair (`twin_masked`).  ed_twin assumes
+    that the model has the twin symmetry (spin exchange, or particle-hole in
+    nonsu2), as the reference does; with Nspin > 1 the two spin species may
+    differ and the reference warns (ED_SETUP.f90:69-70), so this does too."""
+    if ed_twin:
+        if cfg.ed_mode == "nonsu2" and cfg.Jz_basis:
+            raise NotImplementedError("ed_twin in the Jz basis (get_twin_sector is not Jz-aware)")
+        if cfg.Nspin > 1:
+            import warnings
+
+            warnings.warn("ed_twin with Nspin > 1: the twin symmetry is assumed, not checked",
+                          RuntimeWarning, stacklevel=2)
     out = []
     for s in setup_pointers(cfg):
         if s.dim == 0:
             continue
         if cfg.ed_mode == "nonsu2" and cfg.Jz_basis and cfg.Jz_max and abs(s.q2) > int(2 * cfg.Jz_max_value):
+            continue
+        if ed_twin and twin_masked(cfg, s):
             continue
         out.append(s)
     return out

@@ -36,6 +36,9 @@
  *   ed_sector_nn_moments      <- observables_impurity   ED_OBSERVABLES.f90:48-715 and
  *   ed_sector_expect             local_energy_impurity  ED_OBSERVABLES.f90:726-980
  *                                (their sums over the kept vector's elements)
+ *   ed_sector_twin_vector     <- es_return_cvector      ED_EIGENSPACE.f90:414-445 of a twin entry
+ *                                (twin_sector_order / flip_state ED_SETUP.f90:1123-1186,
+ *                                 get_twin_sector ED_SETUP.f90:1196-1212)
  */
 #ifndef ED_GPU_H
 #define ED_GPU_H
@@ -100,6 +103,8 @@ extern "C" {
                                         Ritz vector mixed in) */
 #define ED_OPT_EIGH_FULLPROBE 0x200000 /* eigh: no plain-Lanczos screen before the thick-restart
                                           degeneracy probe (every probe round runs it in full) */
+#define ED_OPT_TWIN_GATHER 0x1000000 /* twin_vector into this sector (normal mode): the gather
+                                        kernel of the other modes, not the tiled transpose */
 
 /* status codes */
 #define ED_OK              0
@@ -324,6 +329,24 @@ int ed_sector_apply_op(const ed_sector* src, const ed_sector* dst, int32_t op, i
 int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t op, int32_t level,
                            double coef_re, double coef_im, int32_t vtype, const void* src_vec,
                            void* dst_vec, void* stream);
+/* Vector of a twin entry of the state list (es_return_cvector,
+ * ED_EIGENSPACE.f90:414-445; twin_sector_order and flip_state,
+ * ED_SETUP.f90:1123-1186), from its partner's vector:
+ *   dst_vec[i] = src_vec[Order(i)],  Order = argsort(flip_state(map_src)),
+ * i.e. row i of dst holds state s and takes the value of src's row of
+ * flip_state(s); no sign, no conjugation.  flip_state exchanges the two
+ * Ns-bit halves (normal, superc) or complements all 2*Ns bits (nonsu2).
+ * dst must be the twin of src (get_twin_sector, ED_SETUP.f90:1196-1212):
+ * (q2, q1) in normal mode (q1 == q2: the map of the sector onto itself), -sz
+ * in superc, 2*Ns - n in nonsu2.  ED_ERR_ARG, nothing launched: another
+ * sector pair, sectors of different models or devices, Jz_basis sectors
+ * (get_twin_sector knows none), src_vec == dst_vec.  Row-split sectors:
+ * ED_ERR_UNSUPPORTED.  Normal mode runs an LDS-tiled transpose of src's
+ * DimDw x DimUp view unless dst has ED_OPT_TWIN_GATHER; the other modes gather
+ * through src's index tables.  Device pointers, async on `stream`; the model
+ * is assumed to have the twin symmetry, as in the reference. */
+int ed_sector_twin_vector(const ed_sector* src, const ed_sector* dst, int32_t vtype, const void* src_vec,
+                          void* dst_vec, void* stream);
 /* Observables of a kept state from its device-resident vector
  * (observables_impurity ED_OBSERVABLES.f90:48-715, local_energy_impurity
  * ED_OBSERVABLES.f90:726-980; no host copy of the vector, no bdecomp /
