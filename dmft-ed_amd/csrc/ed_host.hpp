@@ -2,8 +2,8 @@
 // error reporting (ed_gpu_last_error's thread-local message), the HIPCK / CK
 // early-return macros, the register budgets of the persistent kernels, and
 // the persistent-launch dispatcher (ed_persist_launch.hip: the k_lanc_persist
-// instantiations live in their own translation unit so the two halves of the
-// library compile in parallel).
+// instantiations live in three translation units of their own, one per
+// (HC, VC) case, so that they compile in parallel with the rest).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,38 +1,21 @@
-// ed_lib.hip — the C-ABI of include/ed_gpu.h on top of ed_kernels.hpp.
-//
-// Sector object = what the reference keeps in module state between
-// build_Hv_sector and delete_Hv_sector (ED_HAMILTONIAN_SHARED.f90:32-34,
-// ED_VARS_GLOBAL.f90:104-105): the basis H%map, the stored H spH0 (here a
-// device SELL-64 matrix) or the matrix-free kernel's tables, plus the
-// device-resident Lanczos workspace.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
+// ed_lib.hip — the sector object's life cycle and the library's process-wide
+// state, the H builders, the plain and persistent Lanczos drivers, the
+// thick-restart eigensolver with its batch and lockstep variants, and their
+// C-ABI entry points (include/ed_gpu.h) with the reference-style singleton
+// API.  The sector object itself is in ed_sector.hpp; the H·v launchers and
+// the entry points that apply an operator to a vector are in ed_hxv.hip.
+#include "ed_sector.hpp"
 
-#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
-#include <mutex>
 #include <thread>
-#include <string>
-#include <map>
-#include <vector>
 
-#include "ed_kernels.hpp"
 #include "ed_persist.hpp"
 #include "ed_trlan.hpp"
 #include "ed_trlbatch.hpp"
 #include "ed_trlmulti.hpp"
-#include "ed_fused.hpp"
-#include "ed_split.hpp"
-#include "ed_tables.hpp"
-#include "ed_host.hpp"
 #include "ed_hosteig.hpp"
-#include "ed_obs.hpp"
-#include "ed_twin.hpp"
 
 using namespace edg;
 
@@ -43,19 +26,11 @@ std::string& ed_err_slot() {
   return e;
 }
 
-static constexpr int kMaxGrid = 65536;  // one thread per row up to 16.7 M rows
-static inline int grid_for(int64_t nthreads) {
-  int64_t b = (nthreads + kBlock - 1) / kBlock;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(b, kMaxGrid));
-}
-// one-off grid reductions (in-kernel ticket): few enough blocks that the
-// ticket word does not serialise (grid-strided kernels)
-static inline int grid_once(int64_t nthreads) { return std::min(grid_for(nthreads), 512); }
 // Blocks of `fn` the whole chip holds at once (occupancy x CUs, a multiple of
 // the 8 XCDs): the grid of a grid-strided kernel whose blocks have equal
 // work, so that no block waits for a second round (a 2,048-block grid at 5
 // resident blocks per CU runs 1,280 + 768).
-static int resident_grid(const void* fn, int block, size_t lds = 0) {
+int resident_grid(const void* fn, int block, size_t lds) {
   static std::mutex mu;
   static std::map<std::pair<const void*, size_t>, int> cache;
   std::lock_guard<std::mutex> lk(mu);
@@ -70,182 +45,6 @@ static int resident_grid(const void* fn, int block, size_t lds = 0) {
   return g;
 }
 
-// -------------------------------------------------------------- sector obj
-struct KronHost {
-  int64_t dimup = 0, dimdw = 0;
-  int degup = 0, degdw = 0, nimp = 0;
-  bool diag_real = true;  // spin-factor diagonals have no imaginary part
-  int32_t *upc = nullptr, *dwc = nullptr;
-  void *upv = nullptr, *dwv = nullptr, *aup = nullptr, *adw = nullptr;
-  double* uimp = nullptr;
-  uint8_t *impu = nullptr, *impd = nullptr;
-  // two-pass form (k_kron_up + k_kron_dw): up-hop words {col:16 | value index:8}
-  bool two = false;
-  int cpt = 0, degU = 0, degD = 0;  // template values: columns per thread, slot bounds
-  uint32_t *upw = nullptr, *dwo = nullptr;
-  uint8_t* dwi = nullptr;
-  void *updict = nullptr, *dwdict = nullptr;
-  int nupdict = 0, ndwdict = 0;
-};
-
-struct LancWS {
-  int vc = -1;
-  int cap = 0;                  // alpha/beta capacity
-  void *R = nullptr, *P = nullptr, *W = nullptr, *Y = nullptr;
-  LancState* st = nullptr;
-  double* partials = nullptr;   // [kMaxGrid]
-  unsigned int* counter = nullptr;
-  double *alpha = nullptr, *beta = nullptr, *z = nullptr;  // one block: alpha | beta | z, cap+2 each
-  double* h_ab = nullptr;       // pinned host staging for alpha | beta (2*(cap+2)); the persistent kernel of a single run writes it directly
-  hipEvent_t ev[2] = {nullptr, nullptr};  // lanc_run timing
-  void* basis = nullptr;
-  int basis_cols = 0;
-};
-
-struct ed_sector {
-  int device = 0;
-  std::mutex build_mu;  // lazy table builds (ensure_direct)
-  hipStream_t stream = nullptr;  // private stream for synchronous entry points
-  bool own_stream = true;        // false: the caller's stream (ed_sector_create's argument)
-  EdModel Mh;
-  EdModel* Md = nullptr;
-  SectorTables T;
-  int flags = 0;
-  int opts = 0;        // ED_OPT_* kernel alternatives (ed_sector_set_options)
-  bool hc = true;      // complex H values
-  int64_t dim = 0, nslice = 0;
-  // rows of the operator held here: [row0, row0+nrows) of the sector (the
-  // reference's MPI row split, ED_HAMILTONIAN.f90:55-62); whole sector: 0, dim
-  int64_t row0 = 0, nrows = 0;
-  int32_t* d_off = nullptr;
-  uint32_t* d_rank = nullptr;
-  uint32_t* d_map = nullptr;
-  // stored (SELL-64)
-  void* d_diag = nullptr;
-  int64_t* d_sptr = nullptr;
-  int32_t* d_cols = nullptr;
-  void* d_vals = nullptr;
-  uint16_t* d_cnt = nullptr;
-  int64_t nnz = 0, padded = 0;
-  // packed stored H (real values, <= 256 distinct): {col:24 | index:8} words
-  uint32_t* d_words = nullptr;
-  void* d_pdict = nullptr;   // real(8) or complex(8) values (hc)
-  int npdict = 0;
-  // two-segment stored H (ed_split.hpp): A words (diagonal + in-block
-  // elements, row order), B slices (cross-block elements: U list + L words)
-  bool split = false;
-  int64_t* d_sptrA = nullptr;
-  uint32_t* d_wordsA = nullptr;
-  int64_t paddedA = 0;
-  int wA_max = 0, wA_min = 0;  // widest / narrowest A slice (k_spmv_sa chunk choice)
-  int64_t split_meta = 0, split_listR = 0;  // (ed_sector_info.split_bytes)
-  int split_uch = 8;        // U batch of k_spmv_sb (7 or 8)
-  SplitSlice* d_bsl = nullptr;
-  int nbsl = 0;
-  // k_spmv_sb work lists (half-chunk-major), each cut into 8 per-XCD ranges:
-  // real vectors: items of two 64-row halves of pair slices + the generic
-  // slices; complex vectors: every half
-  int2* d_itR = nullptr;
-  int* d_glist = nullptr;
-  int* d_xoff = nullptr;    // [27]: items R | generic | items C ranges
-  int2* d_ul = nullptr;
-  uint32_t* d_lw = nullptr;
-  int64_t nul = 0, nlw = 0, nfar = 0, nfar_u = 0;  // U entries, L words, cross-block elements (all / in U)
-  // fused one-pass re-laid stored H (ed_fused.hpp): 64-row units of one idw
-  // block with A words (in-block), U list (unit-uniform cross-block), L words
-  bool fused = false;
-  FuUnit* d_fu = nullptr;
-  int64_t nfu = 0;
-  uint32_t* d_fa = nullptr;
-  int2* d_ful = nullptr;
-  uint32_t* d_flw = nullptr;
-  int64_t fu_na = 0, fu_nu = 0, fu_nl = 0, fu_far = 0, fu_far_u = 0;  // A words, U entries, L words, cross (all / U)
-  int fu_wa_max = 0, fu_wa_min = 0, fu_uch = kFuUChunk;
-  // matrix-free, generic (k_direct): chunk list, per-block op lists, 16-bit tables
-  DirChunk* d_dchunk = nullptr;   // 64-row chunks (real vectors)
-  int ndchunk = 0;
-  DirChunk* d_dchunk2 = nullptr;  // 128-row chunks (complex vectors, two rows per lane)
-  int ndchunk2 = 0;
-  DirGroup* d_dops = nullptr;
-  uint16_t *d_rank16 = nullptr, *d_pat16 = nullptr;
-  void* d_ddiag = nullptr;   // gen_diag of the sector object's rows (k_gen_diag)
-  bool dir_patlds = false;
-  int dir_lds = 0, dir_grid = 0;
-  // matrix-free, Kronecker form
-  bool kron = false;
-  KronHost K;
-  // host-pointer H·v staging
-  void *d_x = nullptr, *d_y = nullptr;
-  LancWS ws;
-  int64_t bytes = 0;
-  std::vector<void*> allocs;
-  // persistent one-workgroup Lanczos (small sectors)
-  double pthresh = 0.0;     // breakdown threshold of the current persistent run
-  // the last persist_mode answer and its LDS bytes, valid for (vc, path, opts);
-  // one entry: the mode's tables (MODE 4: per path) are those of the last answer
-  struct {
-    int vc = -1, path = -3, opts = 0, mode = -1;
-    int64_t lds = 0;
-  } pchoice;
-  // register-resident stored matrix for the persistent kernel (MODE 2)
-  int preg_E = 0;           // 0 not built, -1 ineligible, else ELL row width W
-  int preg_rpt = 0;         // rows per thread (template value)
-  int kreg_W = 0, kreg_rpt = 0;  // MODE 3 (Kronecker words in registers)
-  uint32_t* d_pk = nullptr;
-  void* d_dict = nullptr;
-  int ndict = 0;
-  // Kronecker register layout for the persistent kernel (MODE 4)
-  int pkr_state = 0;        // 0 not tried, -1 ineligible, 1 tables ready
-  int pkr_src = -1;         // path the tables came from (0 stored SELL, 2 hop tables)
-  int pkr_E = 0, pkr_rpt = 0, pkr_du = 0, pkr_dd = 0, pkr_degu = 0, pkr_degd = 0;
-  const int32_t *d_kupc = nullptr, *d_kdwc = nullptr;
-  const double *d_kupv = nullptr, *d_kdwv = nullptr, *d_kdiag = nullptr;
-  // graph cache for Lanczos iterations
-  hipGraphExec_t gexec = nullptr;
-  int g_path = -2, g_vc = -1, g_chunk = 0;
-  bool g_basis = false;
-};
-
-// All device memory and copies of a sector are ordered on its private stream
-// (stream-ordered allocator, async copies + a stream sync): no call here
-// synchronises the device or the null stream, so sectors can be built,
-// solved (graph capture included) and freed from several host threads at
-// once (farm workers).
-static int dcopy(const ed_sector* s, void* dst, const void* src, size_t n, hipMemcpyKind k) {
-  HIPCK(hipMemcpyAsync(dst, src, n, k, s->stream));
-  HIPCK(hipStreamSynchronize(s->stream));
-  return ED_OK;
-}
-static int dalloc(ed_sector* s, void** p, size_t n) {
-  if (n == 0) n = 16;
-  hipError_t e = hipMallocAsync(p, n, s->stream);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return fail(e == hipErrorOutOfMemory ? ED_ERR_OOM : ED_ERR_HIP,
-                std::string("hipMalloc(") + std::to_string(n) + ") -> " + hipGetErrorString(e));
-  }
-  s->allocs.push_back(*p);
-  s->bytes += (int64_t)n;
-  return ED_OK;
-}
-static void dfree(ed_sector* s, void** p, size_t n) {
-  if (!*p) return;
-  auto it = std::find(s->allocs.begin(), s->allocs.end(), *p);
-  if (it != s->allocs.end()) s->allocs.erase(it);
-  (void)hipFreeAsync(*p, s->stream);
-  s->bytes -= (int64_t)n;
-  *p = nullptr;
-}
-template <class T>
-static int dalloc_t(ed_sector* s, T** p, size_t count) {
-  return dalloc(s, (void**)p, count * sizeof(T));
-}
-template <class T>
-static int upload(ed_sector* s, T** p, const std::vector<T>& h) {
-  CK(dalloc_t(s, p, h.size()));
-  return dcopy(s, *p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-
 // Pinned host staging, every buffer of the library (a sector's plain-Lanczos
 // alpha|beta copies; the thick-restart, batch and lockstep solves' per-call
 // staging through PinnedLease), from a process-wide pool that only grows:
@@ -256,7 +55,7 @@ static int upload(ed_sector* s, T** p, const std::vector<T>& h) {
 static std::mutex g_pin_mu;
 static std::multimap<size_t, void*> g_pin_free;  // free blocks by size
 static std::map<void*, size_t> g_pin_size;       // every block ever allocated
-static void* pinned_get(size_t n) {
+void* pinned_get(size_t n) {
   {
     std::lock_guard<std::mutex> lk(g_pin_mu);
     auto it = g_pin_free.lower_bound(n);
@@ -273,32 +72,11 @@ static void* pinned_get(size_t n) {
   g_pin_size[p] = n;
   return p;
 }
-static void pinned_put(void* p) {
+void pinned_put(void* p) {
   if (!p) return;
   std::lock_guard<std::mutex> lk(g_pin_mu);
   g_pin_free.emplace(g_pin_size[p], p);
 }
-// A pool block for one solve on stream st, returned only once st is idle (it
-// is on the success path; after an early error return a copy may still be in
-// flight, and the block must not reach another thread under it).
-struct PinnedLease {
-  void* const p;
-  const hipStream_t st;
-  PinnedLease(size_t n, hipStream_t st_) : p(pinned_get(n)), st(st_) {}
-  PinnedLease(const PinnedLease&) = delete;
-  ~PinnedLease() {
-    if (!p) return;
-    (void)hipStreamSynchronize(st);
-    pinned_put(p);
-  }
-};
-struct DevFree {  // hipFreeAsync of one device block at scope exit
-  void* p;
-  hipStream_t st;
-  ~DevFree() { (void)hipFreeAsync(p, st); }
-};
-// sub-arrays of a device slice of doubles start on 16-byte boundaries (double2)
-static inline size_t even(size_t q) { return (q + 1) & ~(size_t)1; }
 
 static void sector_free(ed_sector* s) {
   if (!s) return;
@@ -403,27 +181,10 @@ static int build_pack(ed_sector* s) {
   return ED_OK;
 }
 
-// Row-split sectors (ed_sector_create_rows) hold rows [row0, row0+nrows) of
-// H: H·v from a whole-sector vector and the CSR dump only.
-static int whole_only(const ed_sector* s) {
-  if (s->nrows == s->dim) return ED_OK;
-  return fail(ED_ERR_UNSUPPORTED, "row-split sector: only ed_sector_hxv_dev[_path] and ed_sector_dump_csr apply");
-}
-
-// Bytes of the stored matrix stream (the NT threshold: beyond ~192 MB it
-// cannot stay in the 256 MB MALL next to the vectors).
-static int64_t stored_mbytes(const ed_sector* s) {
-  const int64_t hv = s->hc ? 16 : 8;
-  if (s->d_words) return s->padded * 4 + s->nrows * hv;
-  return s->padded * (4 + hv) + s->nrows * hv;
-}
-
 // ---------------------------------------------------- two-segment stored H
 // (ed_split.hpp).  Built for whole packed sectors whose stored matrix does
 // not fit the 256 MB Infinity Cache (the sectors whose one-pass kernel pays
 // the down-spin re-gathers from HBM).
-static constexpr int64_t kSplitMinBytes = (int64_t)192 << 20;
-
 static int build_split(ed_sector* s) {
   const int64_t dim = s->dim, ns = s->nslice;
   const int hw = s->hc ? 2 : 1;
@@ -1084,7 +845,7 @@ static int build_direct(ed_sector* s) {
 
 // the k_direct tables on first use of path 1 (build_direct), ordered before
 // the caller's stream by a sync of the sector's stream
-static int ensure_direct(ed_sector* s, int path, hipStream_t caller = nullptr) {
+int ensure_direct(ed_sector* s, int path, hipStream_t caller) {
   if (path != 1 || s->nrows == 0) return ED_OK;
   // one builder per sector (two threads' first path-1 H·v would race on the
   // tables); a stream being graph-captured cannot take the build's syncs
@@ -1098,37 +859,6 @@ static int ensure_direct(ed_sector* s, int path, hipStream_t caller = nullptr) {
   if (!(s->flags & ED_DIRECT)) return fail(ED_ERR_ARG, "generic matrix-free path needs ED_DIRECT");
   CK(build_direct(s));
   HIPCK(hipStreamSynchronize(s->stream));
-  return ED_OK;
-}
-
-template <bool HC, bool VC, bool PL, class Epi>
-static int launch_direct(ed_sector* s, const void* x, Epi epi, hipStream_t st) {
-  using V = val_t<VC>;
-  // the gathers address x through a 4 GiB buffer resource with 32-bit byte
-  // offsets (ld_rsrc): a longer vector would read zeros past the range
-  if ((uint64_t)s->dim * sizeof(V) > kDirMaxVecBytes)
-    return fail(ED_ERR_UNSUPPORTED, "k_direct: vector of " + std::to_string(s->dim) +
-                                        " elements exceeds the 4 GiB gather range (use the stored or Kronecker path)");
-  constexpr int R = VC ? kDirRows : 1;
-  auto fn = k_direct<HC, VC, PL, R, Epi>;
-  // dynamic LDS beyond 64 KB: allow what the 160 KB leave next to the
-  // function's static LDS (the epilogue's reduction slots)
-  static std::once_flag attr;
-  static hipError_t ae = hipSuccess;
-  std::call_once(attr, [&]() {
-    hipFuncAttributes fa{};
-    ae = hipFuncGetAttributes(&fa, (const void*)fn);
-    if (ae == hipSuccess)
-      ae = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               160 * 1024 - (int)fa.sharedSizeBytes);
-  });
-  if (ae != hipSuccess) {
-    (void)hipGetLastError();  // not sticky for later launches
-    return fail(ED_ERR_HIP, std::string("k_direct LDS attribute -> ") + hipGetErrorString(ae));
-  }
-  hipLaunchKernelGGL(fn, dim3(s->dir_grid), dim3(kDirBlock), s->dir_lds, st, (const val_t<HC>*)s->d_ddiag,
-                     R == 1 ? s->d_dchunk : s->d_dchunk2, R == 1 ? s->ndchunk : s->ndchunk2,
-                     s->d_dops, s->d_rank16, s->d_pat16, s->d_map, s->T.ns, (const V*)x, s->dim, s->row0, epi);
   return ED_OK;
 }
 
@@ -1336,361 +1066,6 @@ static int build_kron(ed_sector* s) {
     for (int y = 0; y < K.nimp; y++) u[(size_t)x * K.nimp + y] = hint_value(M, (uint32_t)x, (uint32_t)y);
   CK(upload(s, &K.uimp, u));
   return ED_OK;
-}
-
-template <bool HC>
-static KronArgs<HC> kron_args(const ed_sector* s) {
-  using H = val_t<HC>;
-  KronArgs<HC> a;
-  a.dimup = s->K.dimup; a.dimdw = s->K.dimdw; a.degup = s->K.degup; a.degdw = s->K.degdw;
-  a.nimp = s->K.nimp;
-  a.upc = s->K.upc; a.upv = (const H*)s->K.upv; a.dwc = s->K.dwc; a.dwv = (const H*)s->K.dwv;
-  a.aup = (const H*)s->K.aup; a.adw = (const H*)s->K.adw; a.uimp = s->K.uimp;
-  a.impu = s->K.impu; a.impd = s->K.impd;
-  return a;
-}
-
-// ------------------------------------------------------------ H·v launch
-// path: 0 = stored SELL, 1 = direct generic, 2 = direct Kronecker, -1 = default
-static int resolve_path(const ed_sector* s, int path) {
-  if (path == -1) {
-    if (s->flags & ED_STORED) return 0;
-    return s->kron ? 2 : 1;
-  }
-  if (path == 0 && !(s->flags & ED_STORED)) return -1;
-  if (path == 2 && !s->kron) return -1;
-  if (path < 0 || path > 2) return -1;
-  return path;
-}
-
-// XCD-aware block order for the stored kernels (each XCD sweeps one row
-// range, so its L2 serves the v gathers of neighbouring rows): n28 packed
-// 0.240 -> 0.230 ms, c4 0.0193 -> 0.0173 ms.  The grid is then a multiple of
-// 8; every per-block reduction over an H·v launch must use hxv_blocks().
-// Only the packed kernel on grids of >= 1024 blocks gains (plain SELL n28:
-// 0.421 -> 0.443 ms with the remap; small grids lose blocks to the rounding).
-static bool xcd_on(const ed_sector* s, int path) {
-  return path == 0 && s->d_words && grid_for(s->nslice * 64) >= 1024;
-}
-// pass D of the two-pass Kronecker H·v: a multiple of 8 blocks (XCD column
-// chunks), 8 resident per CU
-static constexpr int kKronDwGrid = 2048;
-static constexpr int kKronDwGrid2 = 1280;  // two columns per lane
-// pass U LDS: dictionary + two sets of `rows` staged rows
-static constexpr int kKronUpSets = 2;
-static size_t kron_up_lds(bool hc, bool vc, int64_t du, int rows) {
-  return kKronDictMax * (hc ? 16 : 8) + kKronUimpMax * 8 + kKronUpSets * rows * (size_t)((du + 1) & ~1) * (vc ? 16 : 8);
-}
-static int kron_up_rows(bool hc, bool vc, int64_t du) { return kron_up_lds(hc, vc, du, 2) <= 160 * 1024 ? 2 : 1; }
-static bool kron2_on(const ed_sector* s, int path, int vc) {
-  if (path != 2 || !s->K.two) return false;
-  return kron_up_lds(s->hc, vc, s->K.dimup, 1) <= 160 * 1024;
-}
-// pass D grid: kKronDwGrid blocks (a multiple of 8: XCD column chunks).
-// Every per-block reduction of a pass-D epilogue is sized by this (through
-// hxv_blocks).
-// Complex vectors take half the grid: their column chunk V[:, c0:c0+64] is
-// twice the bytes, and fewer chunks in flight keep it in L2 (N28 complex
-// pass D: 512 blocks 187-193 us, 1024 160 us, 2048 167 us; real: 109, 81, 80).
-// The two-column real form (even DimUp) has twice the chunk bytes too and
-// takes 1280 blocks, 5 per CU (N28: 2048 0.111 ms, 1536 0.115, 1280 0.104-
-// 0.106, 1024 0.104, 768 0.106-0.107; N28b 0.134 / 0.129 / 0.126-0.131 /
-// 0.129-0.130 / 0.135; configs[3] (6,6) 0.0150 / 0.0152 / 0.0152-0.0153 /
-// 0.0155 / 0.0161 ms).
-static int kron_dw_grid(const ed_sector* s, bool vc) {
-  if (vc) return kKronDwGrid / 2;
-  // (a launch whose pointers are not 16-byte aligned falls back to the
-  // one-column form on this same grid: hxv_blocks() must match the launch)
-  return s->K.dimup % 2 == 0 ? kKronDwGrid2 : kKronDwGrid;
-}
-// the two-segment stored kernels serve path 0 unless ED_OPT_STORED_EXACT
-// The fused form serves complex(8) vectors, and real vectors where the
-// two-segment form is not built (its y round trip stays in the Infinity Cache
-// for real vectors: N28 0.182 ms against 0.186 fused, gpurun_out r6b).
-static bool fused_on(const ed_sector* s, int path, int vc) {
-  return path == 0 && s->fused && !(s->opts & (ED_OPT_STORED_EXACT | ED_OPT_NO_FUSED)) && (vc || !s->split);
-}
-static bool split_on(const ed_sector* s, int path, int vc = 0) {
-  // (real vectors only: with complex(8) vectors x and y do not fit the
-  // Infinity Cache together and the split is slower than one pass, N28 0.359
-  // against 0.316 ms)
-  return path == 0 && s->split && !vc && !(s->opts & ED_OPT_STORED_EXACT);
-}
-static int fused_grid(const ed_sector* s, int vc);
-static int hxv_blocks(const ed_sector* s, int path, int vc = 0) {
-  if (kron2_on(s, path, vc)) return kron_dw_grid(s, vc);
-  if (fused_on(s, path, vc)) return fused_grid(s, vc);
-  if (split_on(s, path, vc)) return kSplitGrid;
-  if (path == 1) return s->dir_grid;
-  const int g = grid_for(s->nslice * 64);
-  return xcd_on(s, path) ? (g & ~7) : g;
-}
-
-template <bool HC, bool VC, int CPT, int DEGU, int RU>
-static int launch_kron_up_t(ed_sector* s, const void* x, void* y, hipStream_t st, int64_t w0, int64_t nw) {
-  using V = val_t<VC>;
-  using H = val_t<HC>;
-  KronHost& K = s->K;
-  const size_t lds = kron_up_lds(HC, VC, K.dimup, RU);
-  auto fn = k_kron_up<HC, VC, CPT, DEGU, RU>;
-  static thread_local int attr_set = 0;
-  if (!attr_set) {
-    HIPCK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = 1;
-  }
-  static thread_local int up_grid = 0;  // per instantiation and LDS size (occupancy x CUs)
-  static thread_local size_t up_lds = 0;
-  if (!up_grid || up_lds != lds) {
-    up_lds = lds;
-    int per = 0, dev = 0, ncu = 0;
-    HIPCK(hipGetDevice(&dev));
-    HIPCK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)fn, kKronUpBlock, lds));
-    up_grid = std::max(per, 1) * ncu;
-  }
-  // down rows [w0, w0+nw) (the whole sector, or a rank's row block: x, y
-  // are then that block)
-  KronArgs<HC> ka = kron_args<HC>(s);
-  ka.adw += w0;
-  ka.impd += w0;
-  ka.dimdw = nw;
-  hipLaunchKernelGGL(fn, dim3((int)std::min<int64_t>(nw, up_grid)), dim3(kKronUpBlock), lds, st, ka, K.upw,
-                     (const H*)K.updict, K.nupdict, (const V*)x, (V*)y);
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-template <bool HC, bool VC, int CPT, int DEGU>
-static int launch_kron_up(ed_sector* s, const void* x, void* y, hipStream_t st, int64_t w0, int64_t nw) {
-  // two staged rows per step when LDS allows, except at 4 columns x > 8 slots
-  // per thread, where the second row's registers spill (n28b pass U: 97 us
-  // with 2 rows, 67 us with 1)
-  if (!(CPT >= 4 && DEGU > 8) && kron_up_rows(HC, VC, s->K.dimup) == 2)
-    return launch_kron_up_t<HC, VC, CPT, DEGU, 2>(s, x, y, st, w0, nw);
-  return launch_kron_up_t<HC, VC, CPT, DEGU, 1>(s, x, y, st, w0, nw);
-}
-
-// pass U over down rows [w0, w0+nw)
-template <bool HC, bool VC>
-static int launch_kron_up_any(ed_sector* s, const void* x, void* y, hipStream_t st, int64_t w0, int64_t nw) {
-  switch (s->K.cpt * 100 + s->K.degU) {
-    case 108: return launch_kron_up<HC, VC, 1, 8>(s, x, y, st, w0, nw);
-    case 116: return launch_kron_up<HC, VC, 1, 16>(s, x, y, st, w0, nw);
-    case 208: return launch_kron_up<HC, VC, 2, 8>(s, x, y, st, w0, nw);
-    case 112: return launch_kron_up<HC, VC, 1, 12>(s, x, y, st, w0, nw);
-    case 212: return launch_kron_up<HC, VC, 2, 12>(s, x, y, st, w0, nw);
-    case 216: return launch_kron_up<HC, VC, 2, 16>(s, x, y, st, w0, nw);
-    case 408: return launch_kron_up<HC, VC, 4, 8>(s, x, y, st, w0, nw);
-    case 412: return launch_kron_up<HC, VC, 4, 12>(s, x, y, st, w0, nw);
-    case 808: return launch_kron_up<HC, VC, 8, 8>(s, x, y, st, w0, nw);
-    default: return fail(ED_ERR_STATE, "kron2: no instantiation for this geometry");
-  }
-}
-
-// pass D with rows of length ld over columns [0, ncols); ypart may be null
-template <bool HC, bool VC, class Epi>
-static int launch_kron_dw(ed_sector* s, const void* x, const void* ypart, Epi epi, hipStream_t st, int ld,
-                          int ncols) {
-  using V = val_t<VC>;
-  using H = val_t<HC>;
-  KronHost& K = s->K;
-  const int grid = kron_dw_grid(s, VC);
-  if constexpr (!HC && !VC) {
-    // two columns per lane (16-byte gathers) where the rows, the column
-    // range, both vectors and (plain store: one 16-byte store per lane) the
-    // output are 16-byte aligned
-    bool a16 = ((uintptr_t)x % 16) == 0 && ((uintptr_t)ypart % 16) == 0;
-    if constexpr (std::is_same_v<Epi, EpiStore<VC>>) a16 = a16 && ((uintptr_t)epi.hv % 16) == 0;
-    if (ld % 2 == 0 && ncols % 2 == 0 && a16) {
-      if (K.degD == 8)
-        hipLaunchKernelGGL((k_kron_dw<HC, VC, 8, Epi, 2>), dim3(grid), dim3(kBlock), 0, st, kron_args<HC>(s),
-                           K.dwo, K.dwi, (const H*)K.dwdict, K.ndwdict, (const V*)x, (const V*)ypart, epi, ld,
-                           ncols);
-      else if (K.degD == 12)
-        hipLaunchKernelGGL((k_kron_dw<HC, VC, 12, Epi, 2>), dim3(grid), dim3(kBlock), 0, st, kron_args<HC>(s),
-                           K.dwo, K.dwi, (const H*)K.dwdict, K.ndwdict, (const V*)x, (const V*)ypart, epi, ld,
-                           ncols);
-      else
-        hipLaunchKernelGGL((k_kron_dw<HC, VC, 16, Epi, 2>), dim3(grid), dim3(kBlock), 0, st, kron_args<HC>(s),
-                           K.dwo, K.dwi, (const H*)K.dwdict, K.ndwdict, (const V*)x, (const V*)ypart, epi, ld,
-                           ncols);
-      HIPCK(hipGetLastError());
-      return ED_OK;
-    }
-  }
-  if (K.degD == 8)
-    hipLaunchKernelGGL((k_kron_dw<HC, VC, 8, Epi>), dim3(grid), dim3(kBlock), 0, st, kron_args<HC>(s),
-                       K.dwo, K.dwi, (const H*)K.dwdict, K.ndwdict, (const V*)x, (const V*)ypart, epi, ld, ncols);
-  else if (K.degD == 12)
-    hipLaunchKernelGGL((k_kron_dw<HC, VC, 12, Epi>), dim3(grid), dim3(kBlock), 0, st, kron_args<HC>(s),
-                       K.dwo, K.dwi, (const H*)K.dwdict, K.ndwdict, (const V*)x, (const V*)ypart, epi, ld, ncols);
-  else
-    hipLaunchKernelGGL((k_kron_dw<HC, VC, 16, Epi>), dim3(grid), dim3(kBlock), 0, st, kron_args<HC>(s),
-                       K.dwo, K.dwi, (const H*)K.dwdict, K.ndwdict, (const V*)x, (const V*)ypart, epi, ld, ncols);
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-template <bool HC, bool VC, class Epi>
-static int launch_kron2(ed_sector* s, const void* x, Epi epi, hipStream_t st) {
-  void* y = (void*)epi.scratch();
-  CK((launch_kron_up_any<HC, VC>(s, x, y, st, 0, s->K.dimdw)));
-  return launch_kron_dw<HC, VC>(s, x, y, epi, st, (int)s->K.dimup, (int)s->K.dimup);
-}
-
-// Two-segment stored H·v (ed_split.hpp): segment A (diagonal + in-block
-// elements, k_spmv_pk on the A words) writes y into the epilogue's scratch
-// vector, segment B adds the cross-block elements and runs the epilogue.
-template <bool HC, bool VC, class Epi>
-static int launch_split(ed_sector* s, const void* x, Epi epi, hipStream_t st) {
-  using V = val_t<VC>;
-  using H = val_t<HC>;
-  if constexpr (HC || VC) {
-    // (split_on(): real H on real vectors only; the complex forms are not instantiated)
-    return fail(ED_ERR_STATE, "two-segment stored H·v serves real H on real vectors");
-  } else {
-    V* y = (V*)epi.scratch();
-    const int64_t dim = s->dim, ns = s->nslice;
-    const bool nta = (s->paddedA * 4 + dim * (int64_t)sizeof(H)) > kSplitMinBytes;
-    // A: rows of exactly 7 in-block elements (Norb=1, Nbath=13 half filling)
-    // take 7-slot chunks, rows of <= 8 chunks of 8 slots (fewer padding
-    // gathers than 16); two slices per wave
-#define ED_SPA(NTV, CH)                                                                                       \
-  hipLaunchKernelGGL((k_spmv_sa<HC, VC, NTV, CH, ED_SA_R>),                                                    \
-                     dim3(resident_grid((const void*)k_spmv_sa<HC, VC, NTV, CH, ED_SA_R>, kBlock)), dim3(kBlock), 0, st, \
-                     (const H*)s->d_diag, s->d_sptrA, s->d_wordsA, (const H*)s->d_pdict, (const V*)x, y, dim, ns)
-    if (s->wA_max == 7 && s->wA_min == 7) {
-      if (nta) ED_SPA(1, 7);
-      else ED_SPA(0, 7);
-    } else if (s->wA_max <= 8) {
-      if (nta) ED_SPA(1, 8);
-      else ED_SPA(0, 8);
-    } else if (s->wA_max <= 12) {  // (Norb=2: up to 12 in-block elements per row)
-      if (nta) ED_SPA(1, 12);
-      else ED_SPA(0, 12);
-    } else {
-      if (nta) ED_SPA(1, kChunk);
-      else ED_SPA(0, kChunk);
-    }
-#undef ED_SPA
-    HIPCK(hipGetLastError());
-#define ED_SPB(NTV, U)                                                                                        \
-  hipLaunchKernelGGL((k_spmv_sb<HC, VC, NTV, Epi, U>), dim3(kSplitGrid), dim3(kBlock), 0, st, s->d_bsl, s->d_itR, \
-                     s->d_xoff, s->d_glist, s->d_xoff + 9, s->d_ul, s->d_lw, (const H*)s->d_pdict, (const V*)x,   \
-                     (const V*)y, epi)
-    const bool ntb = s->nlw * 4 > kSplitMinBytes;
-    if (s->split_uch == 7) {
-      if (ntb) ED_SPB(1, 7);
-      else ED_SPB(0, 7);
-    } else {
-      if (ntb) ED_SPB(1, kSplitChunk);
-      else ED_SPB(0, kSplitChunk);
-    }
-#undef ED_SPB
-    HIPCK(hipGetLastError());
-    return ED_OK;
-  }
-}
-
-// Fused one-pass re-laid stored H·v (ed_fused.hpp).  Grid: half the
-// resident blocks, a multiple of 8 (one unit range per XCD) — 16 waves per
-// CU keep the window of units an XCD works on (and the neighbour V rows its
-// cross-block gathers read) smaller than the full resident grid does: N28
-// complex H 0.281 -> 0.269 ms, complex vectors on real H 0.275 -> 0.262, N28
-// Jx/Jp real 0.239 -> 0.228; a quarter measured slower (gpurun_out r6f)
-#ifndef ED_FU_GRID_DIV
-#define ED_FU_GRID_DIV 2
-#endif
-static int fused_grid(const ed_sector* s, int vc) {
-  const int g = vc ? resident_grid((const void*)k_spmv_fu<false, true, 1, EpiStore<true>, 8, 8>, kBlock)
-                   : resident_grid((const void*)k_spmv_fu<false, false, 1, EpiStore<false>, 8, 8>, kBlock);
-  (void)s;
-  return std::max(8, (g / ED_FU_GRID_DIV) & ~7);
-}
-
-template <bool HC, bool VC, class Epi>
-static int launch_fused(ed_sector* s, const void* x, Epi epi, hipStream_t st) {
-  using V = val_t<VC>;
-  using H = val_t<HC>;
-  const int g = fused_grid(s, VC);
-  const bool nt = (s->fu_na + s->fu_nl) * 4 + s->dim * (int64_t)sizeof(H) > kSplitMinBytes;
-#define ED_FU(NTV, CH, U)                                                                                      \
-  hipLaunchKernelGGL((k_spmv_fu<HC, VC, NTV, Epi, CH, U>), dim3(g), dim3(kBlock), 0, st, (const H*)s->d_diag,      \
-                     s->d_fu, s->nfu, s->d_fa, s->d_ful, s->d_flw, (const H*)s->d_pdict, (const V*)x, epi)
-#define ED_FU_CH(NTV, U)                                                   \
-  do {                                                                     \
-    if (s->fu_wa_max == 7 && s->fu_wa_min == 7) ED_FU(NTV, 7, U);          \
-    else if (s->fu_wa_max <= 8 || kFuChMax <= 8) ED_FU(NTV, 8, U);         \
-    else if (s->fu_wa_max <= 12 || kFuChMax <= 12) ED_FU(NTV, 12, U);      \
-    else ED_FU(NTV, kChunk, U);                                            \
-  } while (0)
-  if (s->fu_uch == 7) {
-    if (nt) ED_FU_CH(1, 7);
-    else ED_FU_CH(0, 7);
-  } else {
-    if (nt) ED_FU_CH(1, kFuUChunk);
-    else ED_FU_CH(0, kFuUChunk);
-  }
-#undef ED_FU_CH
-#undef ED_FU
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-template <bool HC, bool VC, class Epi>
-static int launch_hxv_t(ed_sector* s, int path, const void* x, Epi epi, hipStream_t st) {
-  using V = val_t<VC>;
-  const int64_t dim = s->nrows, ns = s->nslice;  // rows of this object; x is the whole sector vector
-  const int g = grid_for(ns * 64);
-  const int gx = hxv_blocks(s, path, VC);
-  const int xr = xcd_on(s, path) ? 1 : 0;
-  const V* xo = (const V*)x + s->row0;  // the rows' own entries
-  // non-temporal matrix loads once the matrix cannot stay in the 256 MB MALL
-  const bool nt = stored_mbytes(s) > ((int64_t)192 << 20);
-  // (segment B's pair items load x and y and store the plain epilogue's Hv
-  // = y 16 bytes at a time: an 8-byte aligned view, e.g. a torch slice at an
-  // odd offset, takes the one-pass kernel)
-  if (fused_on(s, path, VC)) return launch_fused<HC, VC>(s, x, epi, st);
-  if (split_on(s, path, VC) && !(((uintptr_t)x | (uintptr_t)epi.scratch()) & 15))
-    return launch_split<HC, VC>(s, x, epi, st);
-  if (path == 0 && s->d_words) {
-    using H = val_t<HC>;
-    if (nt)
-      hipLaunchKernelGGL((k_spmv_pk<HC, VC, 1, Epi>), dim3(gx), dim3(kBlock), 0, st, (const H*)s->d_diag,
-                         s->d_sptr, s->d_words, (const H*)s->d_pdict, (const V*)x, xo, dim, ns, epi, xr);
-    else
-      hipLaunchKernelGGL((k_spmv_pk<HC, VC, 0, Epi>), dim3(gx), dim3(kBlock), 0, st, (const H*)s->d_diag,
-                         s->d_sptr, s->d_words, (const H*)s->d_pdict, (const V*)x, xo, dim, ns, epi, xr);
-  } else if (path == 0) {
-    if (nt)
-      hipLaunchKernelGGL((k_spmv<HC, VC, 1, Epi>), dim3(gx), dim3(kBlock), 0, st,
-                         (const val_t<HC>*)s->d_diag, s->d_sptr, s->d_cols,
-                         (const val_t<HC>*)s->d_vals, (const V*)x, xo, dim, ns, epi, xr);
-    else
-      hipLaunchKernelGGL((k_spmv<HC, VC, 0, Epi>), dim3(gx), dim3(kBlock), 0, st,
-                         (const val_t<HC>*)s->d_diag, s->d_sptr, s->d_cols,
-                         (const val_t<HC>*)s->d_vals, (const V*)x, xo, dim, ns, epi, xr);
-  } else if (path == 1) {
-    const int rc = s->dir_patlds ? launch_direct<HC, VC, true>(s, x, epi, st)
-                                 : launch_direct<HC, VC, false>(s, x, epi, st);
-    if (rc != ED_OK) return rc;
-  } else if (kron2_on(s, path, VC)) {
-    return launch_kron2<HC, VC>(s, x, epi, st);
-  } else {
-    hipLaunchKernelGGL((k_kron<HC, VC, Epi>), dim3(g), dim3(kBlock), 0, st, kron_args<HC>(s),
-                       (const V*)x, dim, ns, epi);
-  }
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-template <bool VC, class Epi>
-static int launch_hxv(ed_sector* s, int path, const void* x, Epi epi, hipStream_t st) {
-  if (s->hc) {
-    if constexpr (VC) return launch_hxv_t<true, true>(s, path, x, epi, st);
-    return fail(ED_ERR_ARG, "complex Hamiltonian needs complex vectors (vtype=1)");
-  }
-  return launch_hxv_t<false, VC>(s, path, x, epi, st);
 }
 
 // ------------------------------------------------------------ Lanczos
@@ -3409,45 +2784,6 @@ static int tm_run(ed_sector* const* secs, const std::vector<int>& which, int nev
   return tb_scatter(S, which, nev, evals, evecs, nconv, nhv, st, fallback);
 }
 
-template <bool HC, bool VC>
-static int kron_split_launch(ed_sector* s, int part, int64_t o, int64_t n, const void* x, void* y, int acc,
-                             hipStream_t st) {
-  using V = val_t<VC>;
-  const int64_t cnt = n * (part == 0 ? s->K.dimup : s->K.dimdw);
-  if (cnt == 0) return ED_OK;
-  // the two-pass kernels serve the split too (pass U on the row block, pass D
-  // on the column strip, ld = nu): same products, same order as
-  // k_kron_rows / k_kron_cols
-  if (kron2_on(s, 2, VC) && !(s->opts & ED_OPT_SPLIT_SIMPLE)) {
-    if (part == 0) return launch_kron_up_any<HC, VC>(s, x, y, st, o, n);
-    EpiStore<VC> e{(V*)y};
-    return launch_kron_dw<HC, VC>(s, x, acc ? y : nullptr, e, st, (int)n, (int)n);
-  }
-  if (part == 0)
-    hipLaunchKernelGGL((k_kron_rows<HC, VC>), dim3(grid_for(cnt)), dim3(kBlock), 0, st, kron_args<HC>(s), o, n,
-                       (const V*)x, (V*)y);
-  else
-    hipLaunchKernelGGL((k_kron_cols<HC, VC>), dim3(grid_for(cnt)), dim3(kBlock), 0, st, kron_args<HC>(s), n,
-                       (const V*)x, (V*)y, acc);
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-static int kron_split(ed_sector* s, int part, int32_t vtype, int64_t o, int64_t n, const void* x, void* y,
-                      int acc, void* stream) {
-  if (!s || !x || !y) return fail(ED_ERR_ARG, "null");
-  if (!s->kron) return fail(ED_ERR_UNSUPPORTED, "sector has no Kronecker form (normal mode without Jx/Jp, ED_DIRECT)");
-  const int64_t lim = part == 0 ? s->K.dimdw : s->K.dimup;
-  if (o < 0 || n < 0 || o + n > lim) return fail(ED_ERR_ARG, "row/column range outside the factor dimension");
-  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
-  if (vtype == 0 && s->hc) return fail(ED_ERR_ARG, "complex H needs vtype=1");
-  HIPCK(hipSetDevice(s->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (s->hc) return kron_split_launch<true, true>(s, part, o, n, x, y, acc, st);
-  return vtype ? kron_split_launch<false, true>(s, part, o, n, x, y, acc, st)
-               : kron_split_launch<false, false>(s, part, o, n, x, y, acc, st);
-}
-
 // ---------------------------------------------------------------- C-ABI
 extern "C" {
 
@@ -3651,70 +2987,6 @@ int ed_sector_get_info(const ed_sector* s, ed_sector_info* info) {
   return ED_OK;
 }
 
-int ed_sector_hxv_dev_path(ed_sector* s, int32_t path, int32_t vtype, const void* v, void* hv,
-                           void* stream) {
-  if (s && s->nrows == 0) return ED_OK;  // no local rows: nothing to write
-  if (!s || !v || !hv) return fail(ED_ERR_ARG, "null");
-  int pth = resolve_path(s, path);
-  if (pth < 0) return fail(ED_ERR_ARG, "H·v path not available for this sector");
-  HIPCK(hipSetDevice(s->device));
-  CK(ensure_direct(s, pth, (hipStream_t)stream));
-  hipStream_t st = (hipStream_t)stream;
-  if (vtype == 1) {
-    EpiStore<true> e{(double2*)hv};
-    return launch_hxv<true>(s, pth, v, e, st);
-  }
-  if (vtype == 0) {
-    EpiStore<false> e{(double*)hv};
-    return launch_hxv<false>(s, pth, v, e, st);
-  }
-  return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
-}
-
-int ed_sector_col_mask(const ed_sector* s, uint32_t* mask_dev, void* stream) {
-  if (!s || !mask_dev) return fail(ED_ERR_ARG, "null");
-  HIPCK(hipSetDevice(s->device));
-  hipStream_t st = (hipStream_t)stream;
-  HIPCK(hipMemsetAsync(mask_dev, 0, (size_t)((s->dim + 31) / 32) * 4, st));
-  if (s->nrows == 0) return ED_OK;
-  DevIndex idx{s->d_off, s->d_rank, s->T.ns, s->T.nst - 1};
-  hipLaunchKernelGGL(k_mark_cols, dim3(grid_for(s->nrows)), dim3(kBlock), 0, st, s->Md, s->d_map + s->row0,
-                     s->nrows, idx, mask_dev);
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-int ed_sector_kron_rows(ed_sector* s, int32_t vtype, int64_t w0, int64_t nw, const void* x, void* y,
-                        void* stream) {
-  return kron_split(s, 0, vtype, w0, nw, x, y, 0, stream);
-}
-
-int ed_sector_kron_cols(ed_sector* s, int32_t vtype, int64_t u0, int64_t nu, const void* xt, void* yt,
-                        int32_t accumulate, void* stream) {
-  return kron_split(s, 1, vtype, u0, nu, xt, yt, accumulate, stream);
-}
-
-int ed_sector_hxv_dev(ed_sector* s, int32_t vtype, const void* v, void* hv, void* stream) {
-  return ed_sector_hxv_dev_path(s, -1, vtype, v, hv, stream);
-}
-
-int ed_sector_hxv(ed_sector* s, int32_t nloc, const double* v, double* hv) {
-  if (!s || !v || !hv) return fail(ED_ERR_ARG, "null");
-  CK(whole_only(s));
-  // directMatVec_cc: "Nloc != dim(isector)" (DIRECT_HxV.f90:50)
-  if ((int64_t)nloc != s->dim) return fail(ED_ERR_ARG, "ed_gpu_hxv ERROR: Nloc != dim(isector)");
-  HIPCK(hipSetDevice(s->device));
-  if (!s->d_x) {
-    CK(dalloc(s, &s->d_x, s->dim * 16));
-    CK(dalloc(s, &s->d_y, s->dim * 16));
-  }
-  HIPCK(hipMemcpyAsync(s->d_x, v, s->dim * 16, hipMemcpyHostToDevice, s->stream));
-  CK(ed_sector_hxv_dev(s, 1, s->d_x, s->d_y, s->stream));
-  HIPCK(hipMemcpyAsync(hv, s->d_y, s->dim * 16, hipMemcpyDeviceToHost, s->stream));
-  HIPCK(hipStreamSynchronize(s->stream));
-  return ED_OK;
-}
-
 int ed_sector_map(const ed_sector* s, uint32_t* map_host) {
   if (!s || !map_host) return fail(ED_ERR_ARG, "null");
   HIPCK(hipSetDevice(s->device));
@@ -3888,6 +3160,18 @@ int ed_sector_lanc_run(ed_sector* s, int32_t vtype, const void* v0_dev, int32_t 
   return ED_OK;
 }
 
+// lanczos_plain_tridiag_c: alanc(iter)=a; if(iter<nitermax)blanc(iter+1)=b; exit if |b|<thr.
+// The n steps of one run, as the caller's alfa[nitermax] / beta[nitermax].
+static void unpack_tridiag(const double* a, const double* b, int n, int nitermax, double* alfa, double* beta,
+                           int32_t* nlanc) {
+  for (int q = 0; q < nitermax; q++) {
+    alfa[q] = q < n ? a[q] : 0.0;
+    beta[q] = (q >= 1 && q <= n) ? b[q] : 0.0;
+  }
+  beta[0] = 0.0;
+  if (nlanc) *nlanc = n;
+}
+
 int ed_sector_lanc_tridiag(ed_sector* s, int32_t vtype, const void* v0, int32_t nitermax,
                            double threshold, double* alfa, double* beta, int32_t* nlanc) {
   if (!s || !alfa || !beta || nitermax < 1) return fail(ED_ERR_ARG, "bad args");
@@ -3901,14 +3185,7 @@ int ed_sector_lanc_tridiag(ed_sector* s, int32_t vtype, const void* v0, int32_t 
   std::vector<double> a(nitermax + 1), b(nitermax + 2);
   LancState hs;
   CK(d.fetch(a.data(), nitermax, b.data(), nitermax + 1, &hs));
-  // lanczos_plain_tridiag_c: alanc(iter)=a; if(iter<nitermax)blanc(iter+1)=b; exit if |b|<thr
-  int n = hs.iter;
-  for (int q = 0; q < nitermax; q++) {
-    alfa[q] = q < n ? a[q] : 0.0;
-    beta[q] = (q >= 1 && q <= n) ? b[q] : 0.0;
-  }
-  beta[0] = 0.0;
-  if (nlanc) *nlanc = n;
+  unpack_tridiag(a.data(), b.data(), hs.iter, nitermax, alfa, beta, nlanc);
   return ED_OK;
 }
 
@@ -3925,16 +3202,6 @@ int ed_sector_lanc_tridiag_batch(ed_sector* s, int32_t vtype, int32_t nseed, con
   LancDriver d;
   CK(make_driver(s, vtype, false, &d));
   const size_t vs = d.vc ? 16 : 8;
-  auto unpack = [&](int k, const double* a, const double* b, int n) {
-    double* al = alfa + (size_t)k * nitermax;
-    double* be = beta + (size_t)k * nitermax;
-    for (int q = 0; q < nitermax; q++) {
-      al[q] = q < n ? a[q] : 0.0;
-      be[q] = (q >= 1 && q <= n) ? b[q] : 0.0;
-    }
-    be[0] = 0.0;
-    if (nlanc) nlanc[k] = n;
-  };
   if (d.pm < 0 || (s->opts & ED_OPT_NO_BATCH)) {
     CK(lanc_prepare(s, d.vc, nitermax, false, 0));
     for (int k = 0; k < nseed; k++) {
@@ -3945,7 +3212,8 @@ int ed_sector_lanc_tridiag_batch(ed_sector* s, int32_t vtype, int32_t nseed, con
       std::vector<double> a(nitermax + 1), b(nitermax + 2);
       LancState hs;
       CK(d.fetch(a.data(), nitermax, b.data(), nitermax + 1, &hs));
-      unpack(k, a.data(), b.data(), hs.iter);
+      unpack_tridiag(a.data(), b.data(), hs.iter, nitermax, alfa + (size_t)k * nitermax,
+                     beta + (size_t)k * nitermax, nlanc ? nlanc + k : nullptr);
     }
     return ED_OK;
   }
@@ -3956,19 +3224,15 @@ int ed_sector_lanc_tridiag_batch(ed_sector* s, int32_t vtype, int32_t nseed, con
   bt.ldp = (int64_t)p_rows(s);
   bt.ldab = 2 * ((int64_t)nitermax + 2);
   hipStream_t st = d.st;
-  void *R = nullptr, *P = nullptr, *ab = nullptr, *sts = nullptr;
-  HIPCK(hipMallocAsync(&R, (size_t)nseed * bt.ldr * vs, st));
-  HIPCK(hipMallocAsync(&P, (size_t)nseed * bt.ldp * vs, st));
-  HIPCK(hipMallocAsync(&ab, (size_t)nseed * bt.ldab * 8, st));
-  HIPCK(hipMallocAsync(&sts, (size_t)nseed * sizeof(LancState), st));
-  auto release = [&]() {
-    (void)hipFreeAsync(R, st);
-    (void)hipFreeAsync(P, st);
-    (void)hipFreeAsync(ab, st);
-    (void)hipFreeAsync(sts, st);
-  };
-  bt.R = R;
-  bt.P = P;
+  // freed on the stream at every return, an allocation failure's included
+  DevFree fR{nullptr, st}, fP{nullptr, st}, fab{nullptr, st}, fsts{nullptr, st};
+  HIPCK(hipMallocAsync(&fR.p, (size_t)nseed * bt.ldr * vs, st));
+  HIPCK(hipMallocAsync(&fP.p, (size_t)nseed * bt.ldp * vs, st));
+  HIPCK(hipMallocAsync(&fab.p, (size_t)nseed * bt.ldab * 8, st));
+  HIPCK(hipMallocAsync(&fsts.p, (size_t)nseed * sizeof(LancState), st));
+  void *const ab = fab.p, *const sts = fsts.p;
+  bt.R = fR.p;
+  bt.P = fP.p;
   bt.st = (LancState*)sts;
   bt.alpha = (double*)ab;
   bt.beta = (double*)ab + nitermax + 2;
@@ -3984,245 +3248,16 @@ int ed_sector_lanc_tridiag_batch(ed_sector* s, int32_t vtype, int32_t nseed, con
     HIPCK(hipMemcpyAsync(hab.data(), ab, hab.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCK(hipMemcpyAsync(hst.data(), sts, nseed * sizeof(LancState), hipMemcpyDeviceToHost, st));
   }
-  release();
   HIPCK(hipStreamSynchronize(st));
   CK(rc);
   for (int k = 0; k < nseed; k++) {
     // a run that never broke down ends with st->iter = nitermax
     const double* a = hab.data() + (size_t)k * bt.ldab;
-    unpack(k, a, a + nitermax + 2, hst[k].iter);
+    unpack_tridiag(a, a + nitermax + 2, hst[k].iter, nitermax, alfa + (size_t)k * nitermax,
+                   beta + (size_t)k * nitermax, nlanc ? nlanc + k : nullptr);
   }
   return ED_OK;
 }
-
-// dst must be exactly the sector the operator maps src into (getCsector /
-// getCDGsector, ED_SETUP.f90:464-495, 590-619, 750-768); otherwise targets
-// would fall outside dst's index tables
-static int check_op_target(const ed_sector* src, const ed_sector* dst, int32_t op, int32_t level) {
-  if (!src || !dst) return fail(ED_ERR_ARG, "null");
-  if (src->device != dst->device) return fail(ED_ERR_ARG, "sectors on different devices");
-  if (op != 0 && op != 1) return fail(ED_ERR_ARG, "op must be 0 (c) or 1 (c^+)");
-  if (level < 0 || level >= 2 * src->Mh.ns || src->Mh.ns != dst->Mh.ns)
-    return fail(ED_ERR_ARG, "level outside the 2*Ns Fock levels / mismatched models");
-  const int ns = src->Mh.ns, d = op == 1 ? 1 : -1, up = level < ns;
-  int e1 = src->T.q1, e2 = src->T.q2;
-  if (src->Mh.mode == ED_MODE_NORMAL) {
-    if (up) e1 += d; else e2 += d;
-  } else if (src->Mh.mode == ED_MODE_SUPERC) {
-    e1 += up ? d : -d;
-  } else {
-    e1 += d;
-    // getCsector_Jz / getCDGsector_Jz (ED_SETUP.f90:769-805): twoJz -/+ (2*Lzdiag(iorb) + Szdiag(ispin))
-    if (src->Mh.jz) e2 += d * (src->Mh.lz2[up ? level : level - ns] + (up ? 1 : -1));
-  }
-  if (dst->Mh.mode != src->Mh.mode || dst->Mh.jz != src->Mh.jz || dst->T.q1 != e1 || dst->T.q2 != e2)
-    return fail(ED_ERR_ARG, "dst is not the sector reached by the operator");
-  return ED_OK;
-}
-
-int ed_sector_apply_op(const ed_sector* src, const ed_sector* dst, int32_t op, int32_t level,
-                       int32_t vtype, const void* src_vec, void* dst_vec, void* stream) {
-  if (!src_vec || !dst_vec) return fail(ED_ERR_ARG, "null");
-  CK(check_op_target(src, dst, op, level));
-  CK(whole_only(src));
-  CK(whole_only(dst));
-  HIPCK(hipSetDevice(src->device));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t vs = vtype ? 16 : 8;
-  HIPCK(hipMemsetAsync(dst_vec, 0, dst->dim * vs, st));
-  DevIndex idx{dst->d_off, dst->d_rank, dst->T.ns, dst->T.nst - 1};
-  if (vtype)
-    hipLaunchKernelGGL(k_apply_op<true>, dim3(grid_for(src->dim)), dim3(kBlock), 0, st, src->d_map,
-                       src->dim, idx, op, level, (const double2*)src_vec, (double2*)dst_vec);
-  else
-    hipLaunchKernelGGL(k_apply_op<false>, dim3(grid_for(src->dim)), dim3(kBlock), 0, st, src->d_map,
-                       src->dim, idx, op, level, (const double*)src_vec, (double*)dst_vec);
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t op, int32_t level,
-                           double coef_re, double coef_im, int32_t vtype, const void* src_vec,
-                           void* dst_vec, void* stream) {
-  if (!src_vec || !dst_vec) return fail(ED_ERR_ARG, "null");
-  if (!vtype && coef_im != 0.0) return fail(ED_ERR_ARG, "complex coefficient needs vtype=1");
-  CK(whole_only(src));
-  CK(whole_only(dst));
-  CK(check_op_target(src, dst, op, level));
-  HIPCK(hipSetDevice(src->device));
-  hipStream_t st = (hipStream_t)stream;
-  DevIndex idx{dst->d_off, dst->d_rank, dst->T.ns, dst->T.nst - 1};
-  if (vtype)
-    hipLaunchKernelGGL(k_apply_op_acc<true>, dim3(grid_for(src->dim)), dim3(kBlock), 0, st,
-                       src->d_map, src->dim, idx, op, level, coef_re, coef_im,
-                       (const double2*)src_vec, (double2*)dst_vec);
-  else
-    hipLaunchKernelGGL(k_apply_op_acc<false>, dim3(grid_for(src->dim)), dim3(kBlock), 0, st,
-                       src->d_map, src->dim, idx, op, level, coef_re, coef_im,
-                       (const double*)src_vec, (double*)dst_vec);
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-// ------------------------------------------------ twin-sector vectors
-// (ed_twin.hpp).  get_twin_sector (ED_SETUP.f90:1196-1212): (nup, ndw) ->
-// (ndw, nup), sz -> -sz, n -> 2*Ns - n; it knows no (n, twoJz) sectors.
-static int check_twin_pair(const ed_sector* src, const ed_sector* dst) {
-  if (!src || !dst) return fail(ED_ERR_ARG, "null");
-  if (src->device != dst->device) return fail(ED_ERR_ARG, "sectors on different devices");
-  const EdModel &a = src->Mh, &b = dst->Mh;
-  if (a.ns != b.ns || a.norb != b.norb || a.nbath != b.nbath || a.nspin != b.nspin || a.mode != b.mode ||
-      a.bath != b.bath || a.jz != b.jz)
-    return fail(ED_ERR_ARG, "sectors of different models");
-  if (a.jz) return fail(ED_ERR_ARG, "twin sectors are not defined in the Jz basis");
-  int e1, e2 = 0;
-  if (a.mode == ED_MODE_NORMAL) {
-    e1 = src->T.q2;
-    e2 = src->T.q1;
-  } else if (a.mode == ED_MODE_SUPERC) {
-    e1 = -src->T.q1;
-  } else {
-    e1 = 2 * a.ns - src->T.q1;
-  }
-  if (dst->T.q1 != e1 || (a.mode == ED_MODE_NORMAL && dst->T.q2 != e2) || dst->dim != src->dim)
-    return fail(ED_ERR_ARG, "dst is not the twin sector of src");
-  return ED_OK;
-}
-
-int ed_sector_twin_vector(const ed_sector* src, const ed_sector* dst, int32_t vtype, const void* src_vec,
-                          void* dst_vec, void* stream) {
-  if (!src_vec || !dst_vec || src_vec == dst_vec) return fail(ED_ERR_ARG, "null or aliased vectors");
-  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
-  CK(check_twin_pair(src, dst));
-  CK(whole_only(src));
-  CK(whole_only(dst));
-  HIPCK(hipSetDevice(src->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t dim = dst->dim;
-  if (src->Mh.mode == ED_MODE_NORMAL && !(dst->opts & ED_OPT_TWIN_GATHER)) {
-    const int64_t R = src->T.dimdw, C = src->T.dimup;  // the partner's view: idw rows, iup fast
-    const int64_t nt = ((R + kTwinTile - 1) / kTwinTile) * ((C + kTwinTile - 1) / kTwinTile);
-    const int g = (int)std::min<int64_t>(nt, 8 * 256);
-    if (vtype)
-      hipLaunchKernelGGL(k_twin_transpose<true>, dim3(g), dim3(kBlock), 0, st, R, C, (const double2*)src_vec,
-                         (double2*)dst_vec);
-    else
-      hipLaunchKernelGGL(k_twin_transpose<false>, dim3(g), dim3(kBlock), 0, st, R, C, (const double*)src_vec,
-                         (double*)dst_vec);
-  } else {
-    const DevIndex idx{src->d_off, src->d_rank, src->T.ns, src->T.nst - 1};
-    const int nb = 2 * src->Mh.ns;
-    const uint32_t full = nb >= 32 ? 0xFFFFFFFFu : (1u << nb) - 1u;
-    if (vtype)
-      hipLaunchKernelGGL(k_twin_gather<true>, dim3(grid_for(dim)), dim3(kBlock), 0, st, dst->d_map, dim, idx,
-                         src->Mh.mode, full, (const double2*)src_vec, (double2*)dst_vec);
-    else
-      hipLaunchKernelGGL(k_twin_gather<false>, dim3(grid_for(dim)), dim3(kBlock), 0, st, dst->d_map, dim, idx,
-                         src->Mh.mode, full, (const double*)src_vec, (double*)dst_vec);
-  }
-  HIPCK(hipGetLastError());
-  return ED_OK;
-}
-
-// ------------------------------------------------ observables of a kept state
-// (ed_obs.hpp).  Both calls make one grid-strided pass over (d_map, vec) on a
-// grid of at most kObsMaxGrid blocks, then one finishing launch that sums
-// every row of block partials in fixed order; the few results come back
-// through a pinned block.  Nothing is kept in the sector object.
-static constexpr int kObsMaxGrid = 1024;
-
-// observables_impurity's diagonal loop (ED_OBSERVABLES.f90:127-158) and the
-// density-density / Hartree sums of local_energy_impurity (:797-943) are
-// linear in these moments.
-int ed_sector_nn_moments(const ed_sector* s, int32_t vtype, const void* vec_dev, int32_t nlev,
-                         const int32_t* levels, double* out, void* stream) {
-  if (!s || !vec_dev || !levels || !out) return fail(ED_ERR_ARG, "null");
-  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
-  static_assert(kObsMaxLev == 6, "launch_nn_moments instantiates 1..6 levels");
-  if (nlev < 1 || nlev > kObsMaxLev) return fail(ED_ERR_ARG, "nlev must be 1..2*ED_MAX_NORB");
-  ObsLevels L{};
-  for (int p = 0; p < nlev; p++) {
-    if (levels[p] < 0 || levels[p] >= 2 * s->Mh.ns) return fail(ED_ERR_ARG, "level outside the 2*Ns Fock levels");
-    L.lev[p] = levels[p];
-  }
-  CK(whole_only(s));
-  HIPCK(hipSetDevice(s->device));
-  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  const int nm = nlev * (nlev + 1) / 2 + 1;
-  const int g = std::min(grid_for(s->dim), kObsMaxGrid);
-  double* d = nullptr;
-  HIPCK(hipMallocAsync((void**)&d, ((size_t)nm * g + nm) * sizeof(double), st));
-  DevFree fr{d, st};
-  PinnedLease pin((size_t)nm * sizeof(double), st);
-  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
-  if (vtype) launch_nn_moments<true>(nlev, g, st, s->d_map, vec_dev, s->dim, L, d);
-  else launch_nn_moments<false>(nlev, g, st, s->d_map, vec_dev, s->dim, L, d);
-  HIPCK(hipGetLastError());
-  hipLaunchKernelGGL(k_obs_finish, dim3(nm), dim3(kBlock), 0, st, d, g, d + (size_t)nm * g);
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(pin.p, d + (size_t)nm * g, (size_t)nm * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  memcpy(out, pin.p, (size_t)nm * sizeof(double));
-  return ED_OK;
-}
-
-// The off-diagonal sums of observables_impurity (ED_OBSERVABLES.f90:556-581,
-// :631-654; magX/magY/phisc expanded, :166-337) and local_energy_impurity
-// (:802-846 hopping, :882-927 spin exchange and pair hopping) as expectation
-// values of operator strings.  Every string is compiled (and rejected if it
-// leaves the sector) before anything is launched.
-int ed_sector_expect(const ed_sector* s, int32_t vtype, const void* vec_dev, int32_t nterm, const int32_t* nops,
-                     const int32_t* levels, const int32_t* ops, double* out, void* stream) {
-  if (!s || !vec_dev || !nops || !levels || !ops || !out) return fail(ED_ERR_ARG, "null");
-  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
-  if (nterm < 1) return fail(ED_ERR_ARG, "nterm must be positive");
-  CK(whole_only(s));
-  const ObsSector os{s->Mh.ns, s->Mh.mode, s->Mh.jz, s->Mh.lz2};
-  const int ntp = (nterm + kObsTile - 1) / kObsTile * kObsTile;  // padded with null terms
-  std::vector<ObsTerm> terms((size_t)ntp, obs_null_term());
-  for (int t = 0, o = 0; t < nterm; t++) {
-    if (nops[t] < 1 || nops[t] > kObsMaxOps)
-      return fail(ED_ERR_ARG, "term " + std::to_string(t) + ": 1..4 operators per string");
-    if (obs_compile(os, nops[t], levels + o, ops + o, &terms[t]) != ED_OK)
-      return fail(ED_ERR_ARG, "term " + std::to_string(t) + ": bad level/op, or the string leaves the sector");
-    o += nops[t];
-  }
-  HIPCK(hipSetDevice(s->device));
-  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  const int g = std::min(grid_for(s->dim), kObsMaxGrid);
-  const int w = vtype ? 2 : 1;  // partial rows per term
-  const size_t nval = (size_t)w * ntp;
-  double* d = nullptr;
-  HIPCK(hipMallocAsync((void**)&d, (nval * g + nval) * sizeof(double), st));
-  DevFree fr{d, st};
-  PinnedLease pin(nval * sizeof(double), st);
-  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
-  const DevIndex idx{s->d_off, s->d_rank, s->T.ns, s->T.nst - 1};
-  for (int t0 = 0; t0 < ntp; t0 += kObsMaxTerms) {
-    const int n = std::min(kObsMaxTerms, ntp - t0);
-    ObsTermList TL;
-    for (int k = 0; k < kObsMaxTerms; k++) TL.t[k] = k < n ? terms[t0 + k] : obs_null_term();
-    double* part = d + (size_t)w * t0 * g;
-    if (vtype)
-      hipLaunchKernelGGL(k_expect<true>, dim3(g), dim3(kBlock), 0, st, s->d_map, (const double2*)vec_dev, s->dim,
-                         idx, TL, n, part);
-    else
-      hipLaunchKernelGGL(k_expect<false>, dim3(g), dim3(kBlock), 0, st, s->d_map, (const double*)vec_dev, s->dim,
-                         idx, TL, n, part);
-    HIPCK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_obs_finish, dim3((unsigned)nval), dim3(kBlock), 0, st, d, g, d + nval * g);
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(pin.p, d + nval * g, nval * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  const double* h = (const double*)pin.p;
-  for (int t = 0; t < nterm; t++) {
-    out[2 * t] = vtype ? h[2 * t] : h[t];
-    out[2 * t + 1] = vtype ? h[2 * t + 1] : 0.0;
-  }
-  return ED_OK;
-}
-
 // Poles of one GF continued fraction: eigenvalues of tridiag(alfa[0:n],
 // beta[1:n]) and the squared first components of the eigenvectors, the
 // quantities add_to_lanczos_gf_nonsu2 takes from tql2 (ED_GF_NONSU2.f90:936,
@@ -4302,13 +3337,7 @@ int ed_sector_lanc_tridiag_dev(ed_sector* s, int32_t vtype, const void* v0_dev, 
   std::vector<double> a(nitermax + 1), b(nitermax + 2);
   LancState hs;
   CK(d.fetch(a.data(), nitermax, b.data(), nitermax + 1, &hs));
-  int n = hs.iter;
-  for (int q = 0; q < nitermax; q++) {
-    alfa[q] = q < n ? a[q] : 0.0;
-    beta[q] = (q >= 1 && q <= n) ? b[q] : 0.0;
-  }
-  beta[0] = 0.0;
-  if (nlanc) *nlanc = n;
+  unpack_tridiag(a.data(), b.data(), hs.iter, nitermax, alfa, beta, nlanc);
   return ED_OK;
 }
 
