@@ -6,6 +6,7 @@
 #include "ed_sector.hpp"
 #include "ed_obs.hpp"
 #include "ed_twin.hpp"
+#include "ed_seed.hpp"
 
 using namespace edg;
 
@@ -488,6 +489,67 @@ int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t o
                        src->d_map, src->dim, idx, op, level, coef_re, coef_im,
                        (const double*)src_vec, (double*)dst_vec);
   HIPCK(hipGetLastError());
+  return ED_OK;
+}
+
+// ------------------------------------------------ fused GF seeds (ed_seed.hpp)
+// Every seed of one (source vector, operator type, target sector) group: the
+// vvinit loops ED_GF_NORMAL.f90:159-174 and :312-344 with their dot_product
+// and divide, as one gather pass over dst's rows and one scale pass.
+static constexpr int kSeedMaxGrid = 1024;  // partials per seed: the cap kObsMaxGrid puts on the observables' grids
+int ed_sector_seed_batch(const ed_sector* src, const ed_sector* dst, int32_t op, int32_t nlev,
+                         const int32_t* levels, int32_t nseed, const double* coef, int32_t vtype,
+                         const void* src_vec, void* seeds, double* norm2, void* stream) {
+  if (!src || !dst || !levels || !coef || !src_vec || !seeds || !norm2) return fail(ED_ERR_ARG, "null");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (nlev < 1 || nlev > kSeedMaxLev) return fail(ED_ERR_ARG, "nlev must be 1..2*ED_MAX_NORB");
+  if (nseed < 1 || nseed > kSeedMaxSeeds) return fail(ED_ERR_ARG, "nseed must be 1..32");
+  SeedTable T{};
+  T.nlev = nlev;
+  T.nseed = nseed;
+  for (int l = 0; l < nlev; l++) {
+    // the kernel's index tables do not bounds-check: every level must map src into dst
+    CK(check_op_target(src, dst, op, levels[l]));
+    for (int k = 0; k < l; k++)
+      if (levels[k] == levels[l]) return fail(ED_ERR_ARG, "levels must be distinct");
+    T.lev[l] = levels[l];
+  }
+  for (int q = 0; q < nseed; q++)
+    for (int l = 0; l < nlev; l++) {
+      T.cr[q][l] = coef[2 * ((size_t)q * nlev + l)];
+      T.ci[q][l] = coef[2 * ((size_t)q * nlev + l) + 1];
+      if (!vtype && T.ci[q][l] != 0.0) return fail(ED_ERR_ARG, "complex coefficient needs vtype=1");
+      if (T.cr[q][l] != 0.0 || T.ci[q][l] != 0.0) T.used[q] |= (uint8_t)(1u << l);
+    }
+  CK(whole_only(src));
+  CK(whole_only(dst));
+  HIPCK(hipSetDevice(src->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t dim = dst->dim;
+  const int g = std::min(grid_for(dim), kSeedMaxGrid);
+  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
+  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
+  DevFree fr{part, st};
+  PinnedLease pin((size_t)nseed * sizeof(double), st);
+  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
+  double* dn = part + (size_t)nseed * g;
+  double* hn = (double*)pin.p;
+  const DevIndex idx{src->d_off, src->d_rank, src->T.ns, src->T.nst - 1};
+  if (vtype) {
+    hipLaunchKernelGGL(k_seed_gather<true>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, op, T,
+                       (const double2*)src_vec, (double2*)seeds, part);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
+  } else {
+    hipLaunchKernelGGL(k_seed_gather<false>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, op, T,
+                       (const double*)src_vec, (double*)seeds, part);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
+  }
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
   return ED_OK;
 }
 

@@ -2,7 +2,10 @@
 
 Mirrors build_gf_normal / lanc_build_gf_normal_c / add_to_lanczos_gf_normal
 (ED_GF_NORMAL.f90:18-92, 116-260, 580-632) for the diagonal components
-G_{aa,ss}.  Per kept state |gs> (energy E_i), orbital a, spin s:
+G_{aa,ss}, and lanc_build_gf_normal_mix_c (ED_GF_NORMAL.f90:279-553) for the
+orbital off-diagonal G_{ab,ss} of hybrid and replica baths (`orbital_pairs`,
+four two-term seeds per pair and kept state, recombined in build_gf).
+Per kept state |gs> (energy E_i), orbital a, spin s:
 
   * seed  c+_{a s}|gs>  in sector getCDGsector(s, isector)  and
           c_{a s}|gs>   in sector getCsector(s, isector),
@@ -58,6 +61,21 @@ class GFOptions:
     # persistent Lanczos launch per group (one workgroup per seed,
     # ed_sector_lanc_tridiag_batch); bit-identical to the per-seed runs
     batch: bool = True
+    # hybrid / replica baths: the orbital off-diagonal G[s, s, a, b] of
+    # build_gf_normal (ED_GF_NORMAL.f90:33-72).  False: orbital-diagonal only
+    orbital_mix: bool = True
+    # batched path: every seed of one (kept state, operator type, target
+    # sector, vector type) group from one ed_sector_seed_batch call, written
+    # straight into the stacked tensor of the batched Lanczos launch.  Only the
+    # summation order of norm2 differs from the per-seed chain
+    fused_seeds: bool = False
+
+
+# fused_seeds: a stacked seed buffer (one batched Lanczos launch) stays under
+# this many bytes; larger groups are tridiagonalised in chunks (a complex seed
+# of a dim 11.8 M sector is 189 MB: 11 seeds per chunk)
+SEED_BUFFER_BYTES = 2 << 30
+SEED_MAX_LEVELS, SEED_MAX_SEEDS = 6, 32   # kSeedMaxLev, kSeedMaxSeeds (csrc/ed_seed.hpp)
 
 
 def matsubara(beta: float, L: int) -> np.ndarray:
@@ -88,9 +106,10 @@ def tridiag_poles(alfa: np.ndarray, beta: np.ndarray, n: int, first_row: bool = 
 class PoleSums:
     """Device side of add_to_lanczos_gf_normal / _nonsu2 (ED_GF_NORMAL.f90:
     620-631, ED_GF_NONSU2.f90:936-950): the frequency grids are uploaded once,
-    G lives in HBM as (Nspin, Nspin, Norb, L) complex arrays, and `add` queues
-    one continued fraction (its poles from ed_tridiag_poles) for component
-    (ispin, jspin, iorb).  `flush` sums every queued fraction in one launch of
+    G lives in HBM as (Nspin, Nspin, Norb, Norb, L) complex arrays, and `add`
+    queues one continued fraction (its poles from ed_tridiag_poles) for
+    component (ispin, jspin, iorb, jorb), or (ispin, jspin, iorb) meaning
+    jorb = iorb.  `flush` sums every queued fraction in one launch of
     ed_gf_add_poles, in queue order and pole by pole (the reference's order of
     additions into G(i))."""
 
@@ -103,13 +122,14 @@ class PoleSums:
         self.nspin, self.norb, self.eps = nspin, norb, float(eps)
         self.wm = torch.from_numpy(np.ascontiguousarray(wm, dtype=np.float64)).to(self.dev)
         self.wr = torch.from_numpy(np.ascontiguousarray(wr, dtype=np.float64)).to(self.dev)
-        self.Gm = torch.zeros((nspin, nspin, norb, len(wm)), dtype=torch.complex128, device=self.dev)
-        self.Gr = torch.zeros((nspin, nspin, norb, len(wr)), dtype=torch.complex128, device=self.dev)
+        self.Gm = torch.zeros((nspin, nspin, norb, norb, len(wm)), dtype=torch.complex128, device=self.dev)
+        self.Gr = torch.zeros((nspin, nspin, norb, norb, len(wr)), dtype=torch.complex128, device=self.dev)
         self._q = []
 
     def add(self, comp, peso_bz, Ei: float, E: np.ndarray, z: np.ndarray, isign: int) -> None:
-        ispin, jspin, iorb = comp
-        c = (ispin * self.nspin + jspin) * self.norb + iorb
+        ispin, jspin, iorb = comp[:3]
+        jorb = comp[3] if len(comp) > 3 else iorb
+        c = ((ispin * self.nspin + jspin) * self.norb + iorb) * self.norb + jorb
         pb = complex(peso_bz)
         self._q.append((c, pb.real, pb.imag, float(Ei), int(isign), np.asarray(E, np.float64),
                         np.asarray(z, np.float64)))
@@ -138,10 +158,8 @@ class PoleSums:
 
     def to_host(self, Gm: np.ndarray, Gr: np.ndarray) -> None:
         """Add the device G into the host (Nspin, Nspin, Norb, Norb, L) arrays."""
-        gm, gr = self.Gm.cpu().numpy(), self.Gr.cpu().numpy()
-        for o in range(self.norb):
-            Gm[:, :, o, o] += gm[:, :, o]
-            Gr[:, :, o, o] += gr[:, :, o]
+        Gm += self.Gm.cpu().numpy()
+        Gr += self.Gr.cpu().numpy()
 
 
 def _seed(src: Sector, dst: Sector, op: int, terms, vec: np.ndarray, cplx: bool):
@@ -236,18 +254,41 @@ def mixed_pairs(cfg: EDConfig):
     return out
 
 
-def _job_list(cfg: EDConfig, states: StateList):
+def orbital_pairs(cfg: EDConfig):
+    """(ispin, iorb, jorb), iorb < jorb, of the orbital off-diagonal components
+    of build_gf_normal (ED_GF_NORMAL.f90:33-50), in the reference's loop order:
+    none for bath_type normal; hybrid: all of them; replica: only where
+    dmft_bath%mask(ispin,ispin,iorb,jorb,1:2) is set (ED_GF_NORMAL.f90:40-42),
+    i.e. |Re or Im impHloc(ispin,ispin,iorb,jorb)| > 1e-6 (init_dmft_bath_mask,
+    ED_BATH/dmft_aux.f90:261-302).  Empty for nonsu2 and superc."""
+    if cfg.ed_mode != "normal" or cfg.bath_type == "normal":
+        return []
+    out = []
+    for s in range(cfg.Nspin):
+        for a in range(cfg.Norb):
+            for b in range(a + 1, cfg.Norb):
+                if cfg.bath_type == "replica":
+                    h = 0j if cfg.impHloc is None else complex(cfg.impHloc[s, s, a, b])
+                    if not (abs(h.real) > 1e-6 or abs(h.imag) > 1e-6):
+                        continue
+                out.append((s, a, b))
+    return out
+
+
+def _job_list(cfg: EDConfig, states: StateList, orbital_mix: bool = True):
     """Every (component, kept state, seed spec) of build_gf in the serial
     accumulation order: diagonal components (ispin, iorb), then for nonSU2 the
-    mixed seeds (ispin != jspin, iorb).  A seed spec is (op, isign, spin of the
-    first level, [(level, coef)], weight)."""
+    mixed seeds (ispin != jspin, iorb), then (normal mode, hybrid / replica
+    bath, `orbital_mix`) the orbital-mixed seeds (ispin, iorb < jorb) of
+    lanc_build_gf_normal_mix_c.  A component is (ispin, jspin, iorb, jorb); a
+    seed spec is (op, isign, spin of the first level, [(level, coef)], weight)."""
     Ns, No, Nsp = cfg.Ns, cfg.Norb, cfg.Nspin
     site = lambda o, s: o + s * Ns          # impIndex(iorb,ispin), 0-based bit
     chans = []
     for ispin in range(Nsp):
         for iorb in range(No):
             i = site(iorb, ispin)
-            chans.append(((ispin, ispin, iorb), ("diag", ispin, iorb),
+            chans.append(((ispin, ispin, iorb, iorb), ("diag", ispin, iorb),
                           [(1, +1, ispin, [(i, 1)], 1.0), (0, -1, ispin, [(i, 1)], 1.0)]))
     pairs = mixed_pairs(cfg)
     if pairs:
@@ -257,11 +298,23 @@ def _job_list(cfg: EDConfig, states: StateList):
             raise NotImplementedError("mixed nonsu2 seeds in the Jz basis")
         for ispin, jspin, iorb in pairs:
             i, j = site(iorb, ispin), site(iorb, jspin)
-            chans.append(((ispin, jspin, iorb), ("mix", ispin, jspin, iorb), [
+            chans.append(((ispin, jspin, iorb, iorb), ("mix", ispin, jspin, iorb), [
                 (1, +1, ispin, [(i, 1), (j, 1)], 1.0),         # (c+_i + c+_j)|gs>      :571-595
                 (0, -1, ispin, [(i, 1), (j, 1)], 1.0),         # (c_i + c_j)|gs>        :654-678
                 (1, +1, ispin, [(i, 1), (j, 1j)], 1j),         # (c+_i + i c+_j)|gs>    :739-763, cnorm2=i*norm2
                 (0, -1, ispin, [(i, 1), (j, -1j)], 1j),        # (c_i - i c_j)|gs>      :823-847
+            ]))
+    if orbital_mix:
+        # lanc_build_gf_normal_mix_c: both levels have spin ispin, so the four
+        # seeds of a pair live in the diagonal channels' target sectors; the
+        # weight of the last two is -xi*norm2 (the nonSU2 routine's is +xi)
+        for ispin, iorb, jorb in orbital_pairs(cfg):
+            i, j = site(iorb, ispin), site(jorb, ispin)
+            chans.append(((ispin, ispin, iorb, jorb), ("orbmix", ispin, iorb, jorb), [
+                (1, +1, ispin, [(i, 1), (j, 1)], 1.0),         # (c+_i + c+_j)|gs>      ED_GF_NORMAL.f90:312-363
+                (0, -1, ispin, [(i, 1), (j, 1)], 1.0),         # (c_i + c_j)|gs>        ED_GF_NORMAL.f90:371-421
+                (1, +1, ispin, [(i, 1), (j, 1j)], -1j),        # (c+_i + i c+_j)|gs>    ED_GF_NORMAL.f90:429-480
+                (0, -1, ispin, [(i, 1), (j, -1j)], -1j),       # (c_i - i c_j)|gs>      ED_GF_NORMAL.f90:488-539
             ]))
     secs = setup_pointers(cfg)
     jobs = []
@@ -329,6 +382,68 @@ def _tridiag_batch(S: Sector, seeds, nlanc: int, real: bool, threshold: float):
     return a, b, n
 
 
+def _device_vec(vec, cplx: bool, device: int):
+    import torch
+
+    dt = torch.complex128 if cplx else torch.float64
+    if isinstance(vec, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(vec.astype(np.complex128 if cplx else np.float64))).to(
+            f"cuda:{device}")
+    return vec.to(device=f"cuda:{device}", dtype=dt).contiguous()
+
+
+def _seed_calls(jobs, members):
+    """Split `members` (jobs of one target sector and vector type) into
+    ed_sector_seed_batch calls: the same kept state and operator type, at most
+    SEED_MAX_SEEDS seeds and SEED_MAX_LEVELS distinct levels.  Yields
+    (k, op, levels, members of the call)."""
+    by = {}
+    for n in members:
+        by.setdefault((jobs[n][2], jobs[n][3][0]), []).append(n)
+    for (k, op), ns in by.items():
+        levels, call = [], []
+        for n in ns:
+            new = [lv for lv, _ in jobs[n][3][3] if lv not in levels]
+            if call and (len(call) == SEED_MAX_SEEDS or len(levels) + len(new) > SEED_MAX_LEVELS):
+                yield k, op, levels, call
+                levels, call = [], []
+                new = list(dict.fromkeys(lv for lv, _ in jobs[n][3][3]))
+            levels += new
+            call.append(n)
+        yield k, op, levels, call
+
+
+def _fused_seeds(cfg, states, jobs, members, cache, cplx: bool):
+    """The normalised seeds of `members` as rows of one device tensor, and
+    their norm2, from ed_sector_seed_batch (csrc/ed_seed.hpp): one call per
+    (kept state, operator type).  Returns (members in row order, tensor, norm2)."""
+    import torch
+
+    HJ = cache.get(jobs[members[0]][5], True)
+    dt = torch.complex128 if cplx else torch.float64
+    out = torch.empty((len(members), HJ.dim), dtype=dt, device=f"cuda:{cache.device}")
+    st = torch.cuda.current_stream(out.device)
+    P = ctypes.c_void_p
+    rows, norms, r0 = [], [], 0
+    for k, op, levels, call in _seed_calls(jobs, members):
+        HI = cache.get(jobs[call[0]][4], False)
+        x = _device_vec(_state_vec(cfg, states, k, cache), cplx, cache.device)
+        coef = np.zeros((len(call), len(levels)), dtype=np.complex128)
+        for q, n in enumerate(call):
+            for lv, c in jobs[n][3][3]:
+                coef[q, levels.index(lv)] = c
+        lev = np.array(levels, dtype=np.int32)
+        n2 = np.zeros(len(call))
+        check(_lib.load().ed_sector_seed_batch(HI.handle, HJ.handle, op, len(levels), P(lev.ctypes.data),
+                                               len(call), P(coef.ctypes.data), 1 if cplx else 0,
+                                               P(x.data_ptr()), P(out[r0].data_ptr()), P(n2.ctypes.data),
+                                               P(st.cuda_stream)), "ed_sector_seed_batch")
+        rows += call
+        norms += list(n2)
+        r0 += len(call)
+    return rows, out, norms
+
+
 def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record=None):
     """The seed loop grouped by (target sector, vector type): each group's
     seeds are built on the device and tridiagonalised in one batched launch;
@@ -350,32 +465,47 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
     fracs = {}
     try:
         for (_, _, cplx), members in groups.items():
-            live, seeds, norms = [], [], []
-            for n in members:
-                comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
-                HI, HJ = cache.get(sec, False), cache.get(jsec, True)
-                seed, norm2 = _seed(HI, HJ, op, terms, _state_vec(cfg, states, k, cache), cplx)
-                if norm2 == 0.0:
-                    continue
-                live.append(n)
-                seeds.append(seed)
-                norms.append(norm2)
-            if not live:
-                continue
-            HJ = cache.get(jobs[live[0]][5], True)
-            nlanc = min(HJ.dim, gopt.lanc_nGFiter)
-            stacked = torch.stack(seeds).contiguous()
-            # the library copies the seeds on the sector's own (non-blocking)
-            # stream: the stack kernel on torch's stream must be complete first
-            torch.cuda.current_stream(stacked.device).synchronize()
-            a, b, nl = _tridiag_batch(HJ, stacked, nlanc, not cplx, gopt.threshold)
-            for q, n in enumerate(live):
-                comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
-                E, z = tridiag_poles(a[q], b[q], nlanc, first_row=True)
-                if record is not None:
-                    record.append((n, dict(channel=tag, isector=states.sectors[k], op=op, norm2=norms[q],
-                                           alfa=a[q], beta=b[q], nlanc=int(nl[q]))))
-                fracs[n] = (comp, _peso_bz(states, k, weight, norms[q], zeta), states.energies[k], E, z, isign)
+            chunks = [members]
+            if gopt.fused_seeds:
+                # rows of one stacked buffer: SEED_BUFFER_BYTES at the most
+                step = max(1, SEED_BUFFER_BYTES // (jobs[members[0]][5].dim * (16 if cplx else 8)))
+                chunks = [members[i:i + step] for i in range(0, len(members), step)]
+            for chunk in chunks:
+                live, seeds, norms = [], [], []
+                if gopt.fused_seeds:
+                    rows, buf, n2 = _fused_seeds(cfg, states, jobs, chunk, cache, cplx)
+                    keep = [q for q, v in enumerate(n2) if v != 0.0]    # norm2 == 0: no fraction
+                    live, norms = [rows[q] for q in keep], [float(n2[q]) for q in keep]
+                    if not live:
+                        continue
+                    stacked = buf if len(keep) == len(rows) else buf[torch.tensor(keep, device=buf.device)]
+                else:
+                    for n in chunk:
+                        comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
+                        HI, HJ = cache.get(sec, False), cache.get(jsec, True)
+                        seed, norm2 = _seed(HI, HJ, op, terms, _state_vec(cfg, states, k, cache), cplx)
+                        if norm2 == 0.0:
+                            continue
+                        live.append(n)
+                        seeds.append(seed)
+                        norms.append(norm2)
+                    if not live:
+                        continue
+                    stacked = torch.stack(seeds).contiguous()
+                HJ = cache.get(jobs[live[0]][5], True)
+                nlanc = min(HJ.dim, gopt.lanc_nGFiter)
+                # the library copies the seeds on the sector's own (non-blocking)
+                # stream: the stack kernel on torch's stream must be complete first
+                torch.cuda.current_stream(stacked.device).synchronize()
+                a, b, nl = _tridiag_batch(HJ, stacked, nlanc, not cplx, gopt.threshold)
+                for q, n in enumerate(live):
+                    comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
+                    E, z = tridiag_poles(a[q], b[q], nlanc, first_row=True)
+                    if record is not None:
+                        record.append((n, dict(channel=tag, isector=states.sectors[k], op=op, norm2=norms[q],
+                                               alfa=a[q], beta=b[q], nlanc=int(nl[q]))))
+                    fracs[n] = (comp, _peso_bz(states, k, weight, norms[q], zeta), states.energies[k], E, z,
+                                isign)
     finally:
         cache.close()
     for n in todo:
@@ -439,10 +569,23 @@ def _dist():
 def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None, device: int = 0,
              record: Optional[list] = None, owners: Optional[List[int]] = None, runner=None):
     """impGmats, impGreal (Nspin, Nspin, Norb, Norb, L) for ed_mode normal
-    (diagonal components, build_gf_normal) and nonsu2 (build_gf_nonsu2,
+    (build_gf_normal, ED_GF_NORMAL.f90:18-92) and nonsu2 (build_gf_nonsu2,
     ED_GF_NONSU2.f90:18-333, bath_type normal/hybrid: diagonal components plus
     the spin-off-diagonal ones from the mixed seeds and the 0.5*(G - (1+i)G_ii -
     (1+i)G_jj) recombination).
+
+    Normal mode: the orbital-diagonal G[s,s,a,a] for every bath; for hybrid and
+    replica baths (`orbital_pairs`, gopt.orbital_mix) also G[s,s,a,b], a < b,
+    from the four seeds (c+_a + c+_b), (c_a + c_b), (c+_a + i c+_b),
+    (c_a - i c_b)|gs> of lanc_build_gf_normal_mix_c (ED_GF_NORMAL.f90:279-553;
+    the last two weighted -i*norm2) and, after the all-reduce,
+      G_ab = 0.5*(G_ab - (1-i) G_aa - (1-i) G_bb),   G_ba = G_ab
+    (ED_GF_NORMAL.f90:61-68).  The copy into G_ba is the reference's choice
+    and is reproduced as it stands: its own comment says the relation holds
+    for a real impHloc_ab only; for a complex one G_ba is NOT the true
+    <c_b (z-H)^-1 c+_a>.  With orbital_mix=False only the diagonal is built;
+    its entries are bit-identical in both settings (the diagonal jobs come
+    first and every component accumulates on its own).
 
     Seed farm: with a process group initialised, the (component, state, seed)
     jobs are split over ranks (longest first by target dimension), each rank
@@ -478,7 +621,8 @@ def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None,
             dist.broadcast_object_list(flag, src=owners[k])
             vecs[k] = broadcast_vector(vecs[k], owners[k], dim, flag[0], device)
         states = states.with_vectors(vecs)
-    jobs, pairs = _job_list(cfg, states)
+    jobs, pairs = _job_list(cfg, states, gopt.orbital_mix)
+    opairs = orbital_pairs(cfg) if gopt.orbital_mix else []
     if world > 1:
         from .farm import lpt_partition
 
@@ -505,8 +649,8 @@ def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None,
         try:
             for n in todo:
                 job = jobs[n]
-                ispin, jspin, iorb = job[0]
-                g_m, g_r = Gm[ispin, jspin, iorb, iorb], Gr[ispin, jspin, iorb, iorb]
+                ispin, jspin, iorb, jorb = job[0]
+                g_m, g_r = Gm[ispin, jspin, iorb, jorb], Gr[ispin, jspin, iorb, jorb]
                 if runner is None:
                     _run_job(cfg, states, gopt, job, cache, poles, record, zeta)
                 else:
@@ -538,18 +682,24 @@ def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None,
             G[ispin, jspin, iorb, iorb] = 0.5 * (G[ispin, jspin, iorb, iorb]
                                                  - (1 + 1j) * G[ispin, ispin, iorb, iorb]
                                                  - (1 + 1j) * G[jspin, jspin, iorb, iorb])
+    for s, a, b in opairs:                         # build_gf_normal, ED_GF_NORMAL.f90:61-68
+        for G in (Gm, Gr):
+            G[s, s, a, b] = 0.5 * (G[s, s, a, b] - (1 - 1j) * G[s, s, a, a] - (1 - 1j) * G[s, s, b, b])
+            G[s, s, b, a] = G[s, s, a, b]
     return Gm, Gr
 
 
 def build_gf_normal(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None,
                     device: int = 0, record: Optional[list] = None):
-    """build_gf_normal (ED_GF_NORMAL.f90:18-92), diagonal components."""
+    """build_gf_normal (ED_GF_NORMAL.f90:18-92).  A record entry of a diagonal
+    channel ("diag", ispin, iorb) gets ispin, iorb and jorb = iorb; one of an
+    orbital-mixed channel ("orbmix", ispin, iorb, jorb) its own jorb."""
     if cfg.ed_mode != "normal":
         raise ValueError("build_gf_normal needs ed_mode='normal'")
     rec = [] if record is not None else None
     Gm, Gr = build_gf(cfg, states, gopt, device, rec)
     if record is not None:
         for r in rec:
-            _, ispin, iorb = r["channel"]
-            record.append(dict(r, ispin=ispin, iorb=iorb))
+            ch = r["channel"]
+            record.append(dict(r, ispin=ch[1], iorb=ch[2], jorb=ch[3] if ch[0] == "orbmix" else ch[2]))
     return Gm, Gr

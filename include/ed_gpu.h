@@ -39,6 +39,8 @@
  *   ed_sector_twin_vector     <- es_return_cvector      ED_EIGENSPACE.f90:414-445 of a twin entry
  *                                (twin_sector_order / flip_state ED_SETUP.f90:1123-1186,
  *                                 get_twin_sector ED_SETUP.f90:1196-1212)
+ *   ed_sector_seed_batch      <- the vvinit loops of lanc_build_gf_normal_c / _mix_c
+ *                                ED_GF_NORMAL.f90:159-174, ED_GF_NORMAL.f90:312-344
  */
 #ifndef ED_GPU_H
 #define ED_GPU_H
@@ -329,6 +331,27 @@ int ed_sector_apply_op(const ed_sector* src, const ed_sector* dst, int32_t op, i
 int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t op, int32_t level,
                            double coef_re, double coef_im, int32_t vtype, const void* src_vec,
                            void* dst_vec, void* stream);
+/* Every Green's-function seed of one (source vector, operator type, target
+ * sector) group in one pass: the vvinit loops ED_GF_NORMAL.f90:159-174 (one
+ * term) and ED_GF_NORMAL.f90:312-344 (two terms) with their dot_product and
+ * divide.  Seed q is
+ *   sum_l coef[q][l] * op_{levels[l]} |src_vec>,  normalised;
+ * norm2[q] = <seed|seed> before normalisation; a seed with norm2 == 0 is left
+ * all zero.  levels: nlev distinct 0-based bits, nlev <= 2*ED_MAX_NORB, every
+ * one reaching the same dst (ED_ERR_ARG otherwise, as ed_sector_apply_op);
+ * coef: [nseed][nlev] (re, im) pairs, host, nseed <= 32, an imaginary part
+ * needs vtype = 1; a coefficient (0, 0) leaves the level out of the seed.
+ * Terms are added in level order: a coefficient 1 followed by coef * second
+ * gives the unnormalised values of ed_sector_apply_op + ed_sector_apply_op_acc
+ * bit for bit.  seeds: device, [nseed][dst->dim], written whole (no memset
+ * needed).  The norms are summed in a fixed order: two calls on the same
+ * input return the same bits.  Row-split sectors: ED_ERR_UNSUPPORTED.
+ * Synchronous on `stream` (norm2 is a host result). */
+int ed_sector_seed_batch(const ed_sector* src, const ed_sector* dst, int32_t op,
+                         int32_t nlev, const int32_t* levels,
+                         int32_t nseed, const double* coef,
+                         int32_t vtype, const void* src_vec,
+                         void* seeds, double* norm2, void* stream);
 /* Vector of a twin entry of the state list (es_return_cvector,
  * ED_EIGENSPACE.f90:414-445; twin_sector_order and flip_state,
  * ED_SETUP.f90:1123-1186), from its partner's vector:
