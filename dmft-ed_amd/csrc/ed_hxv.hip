@@ -423,6 +423,12 @@ int ed_sector_hxv(ed_sector* s, int32_t nloc, const double* v, double* hv) {
 }
 
 
+// what ed_seed_plan.hpp needs to know of a (src, dst) pair
+static SeedSectors seed_sectors(const ed_sector* src, const ed_sector* dst) {
+  return SeedSectors{src->Mh.ns, src->Mh.mode, src->Mh.jz, src->Mh.lz2,
+                     (int32_t)src->T.q1, (int32_t)src->T.q2, (int32_t)dst->T.q1, (int32_t)dst->T.q2};
+}
+
 // dst must be exactly the sector the operator maps src into (getCsector /
 // getCDGsector, ED_SETUP.f90:464-495, 590-619, 750-768); otherwise targets
 // would fall outside dst's index tables
@@ -432,17 +438,10 @@ static int check_op_target(const ed_sector* src, const ed_sector* dst, int32_t o
   if (op != 0 && op != 1) return fail(ED_ERR_ARG, "op must be 0 (c) or 1 (c^+)");
   if (level < 0 || level >= 2 * src->Mh.ns || src->Mh.ns != dst->Mh.ns)
     return fail(ED_ERR_ARG, "level outside the 2*Ns Fock levels / mismatched models");
-  const int ns = src->Mh.ns, d = op == 1 ? 1 : -1, up = level < ns;
-  int e1 = src->T.q1, e2 = src->T.q2;
-  if (src->Mh.mode == ED_MODE_NORMAL) {
-    if (up) e1 += d; else e2 += d;
-  } else if (src->Mh.mode == ED_MODE_SUPERC) {
-    e1 += up ? d : -d;
-  } else {
-    e1 += d;
-    // getCsector_Jz / getCDGsector_Jz (ED_SETUP.f90:769-805): twoJz -/+ (2*Lzdiag(iorb) + Szdiag(ispin))
-    if (src->Mh.jz) e2 += d * (src->Mh.lz2[up ? level : level - ns] + (up ? 1 : -1));
-  }
+  // the sector arithmetic is seed_op_target's (ed_seed_plan.hpp), one definition
+  int32_t e1, e2;
+  if (seed_op_target(seed_sectors(src, dst), op, level, &e1, &e2) != ED_OK)
+    return fail(ED_ERR_ARG, "unknown ed_mode");
   if (dst->Mh.mode != src->Mh.mode || dst->Mh.jz != src->Mh.jz || dst->T.q1 != e1 || dst->T.q2 != e2)
     return fail(ED_ERR_ARG, "dst is not the sector reached by the operator");
   return ED_OK;
@@ -542,6 +541,54 @@ int ed_sector_seed_batch(const ed_sector* src, const ed_sector* dst, int32_t op,
     hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
   } else {
     hipLaunchKernelGGL(k_seed_gather<false>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, op, T,
+                       (const double*)src_vec, (double*)seeds, part);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
+  }
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
+  return ED_OK;
+}
+
+// Seeds whose images mix operator types: the six vvinit loops of
+// lanc_build_gf_superc_c (ED_GF_SUPERC.f90:119-439) per kept state, three per
+// target sector, with their dot_product and divide.  Every check comes before
+// the first launch: a refused call leaves `seeds` untouched.
+int ed_sector_seed_plan(const ed_sector* src, const ed_sector* dst, int32_t nlev, const int32_t* levels,
+                        const int32_t* ops, int32_t nseed, const int32_t* terms, int32_t vtype,
+                        const void* src_vec, void* seeds, double* norm2, void* stream) {
+  if (!src || !dst || !levels || !ops || !terms || !src_vec || !seeds || !norm2) return fail(ED_ERR_ARG, "null");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (nlev < 1 || nlev > kSeedMaxLev) return fail(ED_ERR_ARG, "nlev must be 1..2*ED_MAX_NORB");
+  if (nseed < 1 || nseed > kSeedMaxSeeds) return fail(ED_ERR_ARG, "nseed must be 1..32");
+  // the kernel's index tables do not bounds-check: every image must map src into dst
+  for (int l = 0; l < nlev; l++) CK(check_op_target(src, dst, ops[l], levels[l]));
+  SeedPlan P;
+  if (seed_plan_compile(seed_sectors(src, dst), nlev, levels, ops, nseed, terms, &P) != ED_OK)
+    return fail(ED_ERR_ARG, "seed plan: (level, op) pairs must be distinct, p and q below nlev, p != q");
+  CK(whole_only(src));
+  CK(whole_only(dst));
+  HIPCK(hipSetDevice(src->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t dim = dst->dim;
+  const int g = std::min(grid_for(dim), kSeedMaxGrid);
+  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
+  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
+  DevFree fr{part, st};
+  PinnedLease pin((size_t)nseed * sizeof(double), st);
+  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
+  double* dn = part + (size_t)nseed * g;
+  double* hn = (double*)pin.p;
+  const DevIndex idx{src->d_off, src->d_rank, src->T.ns, src->T.nst - 1};
+  if (vtype) {
+    hipLaunchKernelGGL(k_seed_plan<true>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
+                       (const double2*)src_vec, (double2*)seeds, part);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
+  } else {
+    hipLaunchKernelGGL(k_seed_plan<false>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
                        (const double*)src_vec, (double*)seeds, part);
     HIPCK(hipGetLastError());
     hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);

@@ -29,13 +29,17 @@
 //                  seed with norm2 == 0 stays all zero.  Block 0 of a seed
 //                  stores norm2.  No floating-point atomics: two calls on the
 //                  same input give the same bits.
+//   k_seed_plan    the same gather form for groups whose images mix operator
+//                  types (ed_sector_seed_plan; the superconducting seeds of
+//                  ED_GF_SUPERC.f90:119-439): image l is op_l on level_l
+//                  (seed_image, ed_seed_plan.hpp), a seed is image p or image
+//                  p + image q with unit coefficients.  The kernel argument is
+//                  a SeedPlan of about 90 bytes instead of SeedTable's 3 KB.
 #pragma once
 #include "ed_kernels.hpp"
+#include "ed_seed_plan.hpp"  // kSeedMaxLev, kSeedMaxSeeds, SeedPlan, seed_image
 
 namespace edg {
-
-constexpr int kSeedMaxLev = 2 * ED_MAX_NORB;  // distinct levels of one call
-constexpr int kSeedMaxSeeds = 32;             // seeds of one call
 
 // Levels and coefficients: a kernel argument, the same in every lane (scalar
 // loads).  A coefficient (0, 0) means the level is not part of the seed.
@@ -108,6 +112,62 @@ __global__ void __launch_bounds__(kBlock) k_seed_gather(const uint32_t* __restri
 #pragma unroll
   for (int q = 0; q < kSeedMaxSeeds; q++)
     if (q < T.nseed) block_partial(n2[q], partials + (size_t)q * gridDim.x);
+}
+
+// seeds: [P.nseed][dim] (unnormalised on exit); partials: [P.nseed][gridDim.x].
+// The host has checked (seed_plan_compile) that every image maps src into
+// dst, so every source state of a hit lies in idx_src's tables; a miss looks
+// nothing up.  u_l = sg_l * v_l is what k_apply_op stores, u_p + u_q what
+// k_apply_op_acc with coefficient 1 leaves: the chain's values.  The plan is
+// the same in every lane, so the selects below are on scalar conditions; the
+// images are never indexed by a run-time value (that would put them in
+// scratch).
+template <bool VC>
+__global__ void __launch_bounds__(kBlock) k_seed_plan(const uint32_t* __restrict__ map_dst, int64_t dim,
+                                                      DevIndex idx_src, SeedPlan P,
+                                                      const val_t<VC>* __restrict__ x,
+                                                      val_t<VC>* __restrict__ seeds,
+                                                      double* __restrict__ partials) {
+  using V = val_t<VC>;
+  double n2[kSeedMaxSeeds];
+#pragma unroll
+  for (int s = 0; s < kSeedMaxSeeds; s++) n2[s] = 0.0;
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < dim; r += (int64_t)gridDim.x * kBlock) {
+    const uint32_t t = map_dst[r];
+    V u[kSeedMaxLev];
+#pragma unroll
+    for (int l = 0; l < kSeedMaxLev; l++) {
+      u[l] = vzero<V>();
+      if (l < P.nlev) {
+        uint32_t s;
+        double sg;
+        if (seed_image(t, P.lev[l], P.op[l], &s, &sg)) u[l] = scl(sg, x[idx_src(s)]);
+      }
+    }
+    // A zero the compiler cannot see through, renewed per row: without it the
+    // 2 * 6 * 32 comparisons below are loop-invariant, get hoisted as 64-bit
+    // lane masks and spill (979 SGPRs); with it they are scalar compares next
+    // to their selects.
+    int z = 0;
+    asm volatile("" : "+s"(z));
+#pragma unroll
+    for (int s = 0; s < kSeedMaxSeeds; s++) {
+      if (s < P.nseed) {
+        V a = vzero<V>(), b = vzero<V>();
+#pragma unroll
+        for (int l = 0; l < kSeedMaxLev; l++) {
+          if (P.p[s] == l + z) a = u[l];
+          if (P.q[s] == l + z) b = u[l];
+        }
+        if (P.q[s] != kSeedNone) a = add(a, b);
+        seeds[(size_t)s * dim + r] = a;
+        n2[s] += seed_abs2(a);
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < kSeedMaxSeeds; s++)
+    if (s < P.nseed) block_partial(n2[s], partials + (size_t)s * gridDim.x);
 }
 
 // grid (blocks per seed, nseed).  npart: the gather's grid.

@@ -59,6 +59,7 @@ SIGNATURES = {
     "ed_sector_apply_op": ([_P, _P, _i32, _i32, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_apply_op_acc": ([_P, _P, _i32, _i32, _f64, _f64, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_seed_batch": ([_P, _P, _i32, _i32, _P, _i32, _P, _i32, _P, _P, _P, _P], ctypes.c_int),
+    "ed_sector_seed_plan": ([_P, _P, _i32, _P, _P, _i32, _P, _i32, _P, _P, _P, _P], ctypes.c_int),
     "ed_sector_twin_vector": ([_P, _P, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_nn_moments": ([_P, _i32, _P, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_expect": ([_P, _i32, _P, _i32, _P, _P, _P, _P, _P], ctypes.c_int),

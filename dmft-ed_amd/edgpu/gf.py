@@ -23,6 +23,10 @@ The pole sums of all seeds run in one device kernel (ed_gf_add_poles) into
 G arrays kept in HBM, in the serial job order and the reference's per-pole
 addition order; the frequency grids are uploaded once per build and G is
 copied to the host (or all-reduced on the device) once at the end.
+
+ed_mode superc: build_gf_superc (ED_GF_SUPERC.f90:18-77, 88-446, 757-803),
+the orbital-diagonal normal G and anomalous F from six seeds per orbital and
+kept state in three aux channels, through the same machinery.
 """
 from __future__ import annotations
 
@@ -67,7 +71,8 @@ class GFOptions:
     # batched path: every seed of one (kept state, operator type, target
     # sector, vector type) group from one ed_sector_seed_batch call, written
     # straight into the stacked tensor of the batched Lanczos launch.  Only the
-    # summation order of norm2 differs from the per-seed chain
+    # summation order of norm2 differs from the per-seed chain.  superc: one
+    # ed_sector_seed_plan call per (kept state, target sector, vector type)
     fused_seeds: bool = False
 
 
@@ -75,7 +80,7 @@ class GFOptions:
 # this many bytes; larger groups are tridiagonalised in chunks (a complex seed
 # of a dim 11.8 M sector is 189 MB: 11 seeds per chunk)
 SEED_BUFFER_BYTES = 2 << 30
-SEED_MAX_LEVELS, SEED_MAX_SEEDS = 6, 32   # kSeedMaxLev, kSeedMaxSeeds (csrc/ed_seed.hpp)
+SEED_MAX_LEVELS, SEED_MAX_SEEDS = 6, 32   # kSeedMaxLev, kSeedMaxSeeds (csrc/ed_seed_plan.hpp)
 
 
 def matsubara(beta: float, L: int) -> np.ndarray:
@@ -111,9 +116,11 @@ class PoleSums:
     component (ispin, jspin, iorb, jorb), or (ispin, jspin, iorb) meaning
     jorb = iorb.  `flush` sums every queued fraction in one launch of
     ed_gf_add_poles, in queue order and pole by pole (the reference's order of
-    additions into G(i))."""
+    additions into G(i)).  With `ncomp` the arrays are (ncomp, L) instead and
+    a component is its flat index (the aux channels of build_gf_superc)."""
 
-    def __init__(self, nspin: int, norb: int, wm: np.ndarray, wr: np.ndarray, eps: float, device: int):
+    def __init__(self, nspin: int, norb: int, wm: np.ndarray, wr: np.ndarray, eps: float, device: int,
+                 ncomp: Optional[int] = None):
         import torch
 
         if not torch.cuda.is_available():
@@ -122,14 +129,20 @@ class PoleSums:
         self.nspin, self.norb, self.eps = nspin, norb, float(eps)
         self.wm = torch.from_numpy(np.ascontiguousarray(wm, dtype=np.float64)).to(self.dev)
         self.wr = torch.from_numpy(np.ascontiguousarray(wr, dtype=np.float64)).to(self.dev)
-        self.Gm = torch.zeros((nspin, nspin, norb, norb, len(wm)), dtype=torch.complex128, device=self.dev)
-        self.Gr = torch.zeros((nspin, nspin, norb, norb, len(wr)), dtype=torch.complex128, device=self.dev)
+        shape = (nspin, nspin, norb, norb) if ncomp is None else (ncomp,)
+        self.ncomp = ncomp
+        self.Gm = torch.zeros(shape + (len(wm),), dtype=torch.complex128, device=self.dev)
+        self.Gr = torch.zeros(shape + (len(wr),), dtype=torch.complex128, device=self.dev)
         self._q = []
 
     def add(self, comp, peso_bz, Ei: float, E: np.ndarray, z: np.ndarray, isign: int) -> None:
-        ispin, jspin, iorb = comp[:3]
-        jorb = comp[3] if len(comp) > 3 else iorb
-        c = ((ispin * self.nspin + jspin) * self.norb + iorb) * self.norb + jorb
+        if self.ncomp is not None:
+            c = int(comp)
+            assert 0 <= c < self.ncomp
+        else:
+            ispin, jspin, iorb = comp[:3]
+            jorb = comp[3] if len(comp) > 3 else iorb
+            c = ((ispin * self.nspin + jspin) * self.norb + iorb) * self.norb + jorb
         pb = complex(peso_bz)
         self._q.append((c, pb.real, pb.imag, float(Ei), int(isign), np.asarray(E, np.float64),
                         np.asarray(z, np.float64)))
@@ -157,7 +170,7 @@ class PoleSums:
               "ed_gf_add_poles")
 
     def to_host(self, Gm: np.ndarray, Gr: np.ndarray) -> None:
-        """Add the device G into the host (Nspin, Nspin, Norb, Norb, L) arrays."""
+        """Add the device G into the host arrays of the same shape."""
         Gm += self.Gm.cpu().numpy()
         Gr += self.Gr.cpu().numpy()
 
@@ -165,7 +178,10 @@ class PoleSums:
 def _seed(src: Sector, dst: Sector, op: int, terms, vec: np.ndarray, cplx: bool):
     """Seed sum_t coef_t * op_{level_t}|vec> on the device (first term assigned,
     the rest accumulated, as the vvinit loops of ED_GF_NORMAL/ED_GF_NONSU2);
-    returns (normalised seed, norm2)."""
+    returns (normalised seed, norm2).  A term is (level, coef) with the seed's
+    `op`, or (level, coef, op_t) with an operator type of its own (the superc
+    seeds c+_up + c_dw, ED_GF_SUPERC.f90:332-349); the library checks per call
+    that every term reaches dst."""
     import torch
 
     real = not cplx
@@ -180,11 +196,11 @@ def _seed(src: Sector, dst: Sector, op: int, terms, vec: np.ndarray, cplx: bool)
     L = _lib.load()
     vt = 0 if real else 1
     xp, yp, sp = ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(st.cuda_stream)
-    (lvl0, c0), rest = terms[0], terms[1:]
-    assert c0 == 1
-    check(L.ed_sector_apply_op(src.handle, dst.handle, op, lvl0, vt, xp, yp, sp), "ed_sector_apply_op")
-    for lvl, c in rest:
-        check(L.ed_sector_apply_op_acc(src.handle, dst.handle, op, lvl, float(np.real(c)), float(np.imag(c)),
+    ops = [t[2] if len(t) > 2 else op for t in terms]
+    assert terms[0][1] == 1
+    check(L.ed_sector_apply_op(src.handle, dst.handle, ops[0], terms[0][0], vt, xp, yp, sp), "ed_sector_apply_op")
+    for (lvl, c, *_), o in zip(terms[1:], ops[1:]):
+        check(L.ed_sector_apply_op_acc(src.handle, dst.handle, o, lvl, float(np.real(c)), float(np.imag(c)),
                                        vt, xp, yp, sp), "ed_sector_apply_op_acc")
     norm2 = float(torch.sum(y.abs() ** 2).item())
     if norm2 > 0:
@@ -216,6 +232,7 @@ class _SectorCache:
 
     def __init__(self, cfg, gopt, device):
         self.cfg, self.gopt, self.device, self.d = cfg, gopt, device, {}
+        self.aux = {}      # small device tensors that live as long as the sectors
 
     def get(self, sec, hamiltonian: bool) -> Sector:
         key = (sec.q1, sec.q2, hamiltonian)
@@ -229,6 +246,7 @@ class _SectorCache:
         for S in self.d.values():
             S.close()
         self.d.clear()
+        self.aux.clear()
 
 
 def mixed_pairs(cfg: EDConfig):
@@ -328,6 +346,41 @@ def _job_list(cfg: EDConfig, states: StateList, orbital_mix: bool = True):
     return jobs, pairs
 
 
+SUPERC_CHANNELS = 3      # auxGmats(1:3,:): G_aa, barG_aa, A_aa (ED_GF_SUPERC.f90:23-24)
+
+
+def _job_list_superc(cfg: EDConfig, states: StateList):
+    """Every (component, kept state, seed spec) of lanc_build_gf_superc_c
+    (ED_GF_SUPERC.f90:88-446) in the order in which each aux channel
+    accumulates: orbital, kept state, then the six seeds.  A component is the
+    flat index iorb * 3 + channel (channel 0: G_aa, 1: barG_aa, 2: A_aa); a
+    seed spec is (op of the first term, isign, 0, [(level, 1, op)], 1.0): every
+    term carries its own operator type.  c+_up and c_dw raise sz by one, c_up
+    and c+_dw lower it; a seed whose target sector does not exist is left out."""
+    Ns = cfg.Ns
+    secs = setup_pointers(cfg)
+    by_sz = {s.q1: s for s in secs}
+    jobs = []
+    for iorb in range(cfg.Norb):
+        up, dw = iorb, iorb + Ns
+        seeds = [                                               # ED_GF_SUPERC.f90
+            (0, +1, +1, [(up, 1, 1)]),                          # c+_up|n>            :119-166
+            (0, -1, -1, [(up, 1, 0)]),                          # c_up|n>             :168-217
+            (1, +1, +1, [(dw, 1, 0)]),                          # c_dw|n>             :219-268
+            (1, -1, -1, [(dw, 1, 1)]),                          # c+_dw|n>            :270-318
+            (2, +1, +1, [(up, 1, 1), (dw, 1, 0)]),              # (c+_up + c_dw)|n>   :320-378
+            (2, -1, -1, [(up, 1, 0), (dw, 1, 1)]),              # (c_up + c+_dw)|n>   :380-439
+        ]
+        for k, isec in enumerate(states.sectors):
+            sec = secs[isec - 1]
+            for chan, dsz, isign, terms in seeds:
+                jsec = by_sz.get(sec.q1 + dsz)
+                if jsec is not None:
+                    jobs.append((iorb * SUPERC_CHANNELS + chan, ("superc", chan, iorb), k,
+                                 (terms[0][2], isign, 0, terms, 1.0), sec, jsec))
+    return jobs
+
+
 def _peso_bz(states: StateList, k: int, weight, norm2: float, zeta: float):
     """pesoBZ of add_to_lanczos_gf_normal (ED_GF_NORMAL.f90:596-601) times the
     seed's weight: norm2 / zeta at T=0; at finite T norm2 exp(-beta (Ei - Egs))
@@ -340,10 +393,55 @@ def _peso_bz(states: StateList, k: int, weight, norm2: float, zeta: float):
     return weight * (norm2 * np.exp(-x) / zeta)
 
 
+def _peso_superc(states: StateList, k: int, weight, norm2: float, zeta: float):
+    """pesoBZ of add_to_lanczos_gf_superc (ED_GF_SUPERC.f90:781-782) times the
+    seed's weight: norm2 / zeta at T=0, norm2 exp(-beta (Ei - Egs)) / zeta at
+    finite T.  Unlike the normal-mode routine it has no beta (Ei - Egs) < 200
+    cut (the cut is commented out there, ED_GF_SUPERC.f90:773-779)."""
+    if not states.finite_t:
+        return weight * norm2 / zeta
+    return weight * (norm2 * np.exp(-states.beta * (states.energies[k] - states.emin)) / zeta)
+
+
+def _peso(cfg: EDConfig):
+    return _peso_superc if cfg.ed_mode == "superc" else _peso_bz
+
+
+def superc_twin_sign(Ns: int, hmap: np.ndarray) -> np.ndarray:
+    """The sign that makes a superc twin entry's vector an eigenvector.
+
+    `state_vector` reorders the partner's vector by flip_state (the two Ns-bit
+    halves exchanged) without a sign, as es_return_cvector does
+    (ED_EIGENSPACE.f90:414-445).  In ed_mode superc that exchange P alone is
+    no symmetry: it sends the pair term deltasc (c+_up c+_dw + h.c.) to minus
+    itself, H(deltasc) -> H(-deltasc).  P followed by the gauge turn
+    c -> i c is one, and in the Fock basis it is the reordering times
+    i^(nup + ndw) (-1)^(nup ndw): within a sector (nup - ndw fixed) that is,
+    up to one overall phase, the real sign (-1)^(ndw (1 + nup)) of the twin
+    sector's row state.  Without it the reordered vector of a sz = +-1 sector
+    of the Ns = 3 test model misses (H - E) v = 0 by 0.96; with it by 1e-15.
+    Returns +-1.0 per row of `hmap` (the twin sector's map)."""
+    m = np.asarray(hmap).astype(np.int64)
+    pc = lambda v: sum((v >> b) & 1 for b in range(Ns))    # noqa: E731
+    nup, ndw = pc(m & ((1 << Ns) - 1)), pc(m >> Ns)
+    return 1.0 - 2.0 * ((ndw * (1 + nup)) & 1)
+
+
 def _state_vec(cfg, states, k, cache):
     """Kept state k's vector; a twin entry's is rebuilt on the device from its
-    partner's with the cache's (matrix-free) sector handles."""
-    return state_vector(cfg, states, k, cache.device, lambda s: cache.get(s, False))
+    partner's with the cache's (matrix-free) sector handles.  A superc twin
+    vector also takes `superc_twin_sign` (kept on the device per twin sector):
+    the Green's function needs eigenvectors."""
+    vec = state_vector(cfg, states, k, cache.device, lambda s: cache.get(s, False))
+    if cfg.ed_mode != "superc" or states.partner(k) is None or vec is None:
+        return vec
+    import torch
+
+    sec = setup_pointers(cfg)[states.sectors[k] - 1]
+    key = ("twin_sign", sec.q1)
+    if key not in cache.aux:
+        cache.aux[key] = torch.from_numpy(superc_twin_sign(cfg.Ns, cache.get(sec, False).map())).to(vec.device)
+    return vec * cache.aux[key]
 
 
 def _run_job(cfg, states, gopt, job, cache, poles, record, zeta):
@@ -352,7 +450,7 @@ def _run_job(cfg, states, gopt, job, cache, poles, record, zeta):
     e_i, vec = states.energies[k], _state_vec(cfg, states, k, cache)
     if vec is None:
         raise ValueError("the Green's function needs the state vectors (keep_vectors=True)")
-    cplx = (not cfg.is_real()) or is_complex_vector(vec) or any(np.imag(c) != 0 for _, c in terms)
+    cplx = (not cfg.is_real()) or is_complex_vector(vec) or any(np.imag(t[1]) != 0 for t in terms)
     HI, HJ = cache.get(sec, False), cache.get(jsec, True)
     seed, norm2 = _seed(HI, HJ, op, terms, vec, cplx)
     if norm2 == 0.0:
@@ -364,7 +462,7 @@ def _run_job(cfg, states, gopt, job, cache, poles, record, zeta):
     if record is not None:
         record.append(dict(channel=tag, isector=states.sectors[k], op=op, norm2=norm2, alfa=a, beta=b,
                            nlanc=n))
-    poles.add(comp, _peso_bz(states, k, weight, norm2, zeta), e_i, E, z, isign)
+    poles.add(comp, _peso(cfg)(states, k, weight, norm2, zeta), e_i, E, z, isign)
 
 
 def _tridiag_batch(S: Sector, seeds, nlanc: int, real: bool, threshold: float):
@@ -444,6 +542,61 @@ def _fused_seeds(cfg, states, jobs, members, cache, cplx: bool):
     return rows, out, norms
 
 
+def _plan_calls(jobs, members):
+    """Split `members` (jobs of one target sector and vector type whose terms
+    carry their own operator type) into ed_sector_seed_plan calls: the same
+    kept state, at most SEED_MAX_SEEDS seeds and SEED_MAX_LEVELS distinct
+    (level, op) images.  Yields (k, images, members of the call)."""
+    by = {}
+    for n in members:
+        by.setdefault(jobs[n][2], []).append(n)
+    for k, ns in by.items():
+        images, call = [], []
+        for n in ns:
+            mine = list(dict.fromkeys((lv, o) for lv, _, o in jobs[n][3][3]))
+            new = [im for im in mine if im not in images]
+            if call and (len(call) == SEED_MAX_SEEDS or len(images) + len(new) > SEED_MAX_LEVELS):
+                yield k, images, call
+                images, call, new = [], [], mine
+            images += new
+            call.append(n)
+        yield k, images, call
+
+
+def _fused_seeds_plan(cfg, states, jobs, members, cache, cplx: bool):
+    """_fused_seeds for seeds whose images mix operator types (superc): one
+    ed_sector_seed_plan call (k_seed_plan, csrc/ed_seed.hpp) per kept state.
+    Returns (members in row order, tensor, norm2)."""
+    import torch
+
+    HJ = cache.get(jobs[members[0]][5], True)
+    dt = torch.complex128 if cplx else torch.float64
+    out = torch.empty((len(members), HJ.dim), dtype=dt, device=f"cuda:{cache.device}")
+    st = torch.cuda.current_stream(out.device)
+    P = ctypes.c_void_p
+    rows, norms, r0 = [], [], 0
+    for k, images, call in _plan_calls(jobs, members):
+        HI = cache.get(jobs[call[0]][4], False)
+        x = _device_vec(_state_vec(cfg, states, k, cache), cplx, cache.device)
+        lev = np.array([lv for lv, _ in images], dtype=np.int32)
+        ops = np.array([o for _, o in images], dtype=np.int32)
+        terms = np.full((len(call), 2), -1, dtype=np.int32)
+        for s, n in enumerate(call):
+            tt = jobs[n][3][3]
+            assert len(tt) <= 2 and all(c == 1 for _, c, _ in tt)     # unit coefficients: all superc needs
+            for j, (lv, _, o) in enumerate(tt):
+                terms[s, j] = images.index((lv, o))
+        n2 = np.zeros(len(call))
+        check(_lib.load().ed_sector_seed_plan(HI.handle, HJ.handle, len(images), P(lev.ctypes.data),
+                                              P(ops.ctypes.data), len(call), P(terms.ctypes.data),
+                                              1 if cplx else 0, P(x.data_ptr()), P(out[r0].data_ptr()),
+                                              P(n2.ctypes.data), P(st.cuda_stream)), "ed_sector_seed_plan")
+        rows += call
+        norms += list(n2)
+        r0 += len(call)
+    return rows, out, norms
+
+
 def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record=None):
     """The seed loop grouped by (target sector, vector type): each group's
     seeds are built on the device and tridiagonalised in one batched launch;
@@ -460,7 +613,7 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
         vec = states.vectors[k if p is None else p]    # a twin's vector has its partner's type
         if vec is None:
             raise ValueError("the Green's function needs the state vectors (keep_vectors=True)")
-        cplx = (not cfg.is_real()) or is_complex_vector(vec) or any(np.imag(c) != 0 for _, c in terms)
+        cplx = (not cfg.is_real()) or is_complex_vector(vec) or any(np.imag(t[1]) != 0 for t in terms)
         groups.setdefault((jsec.q1, jsec.q2, cplx), []).append(n)
     fracs = {}
     try:
@@ -473,7 +626,8 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
             for chunk in chunks:
                 live, seeds, norms = [], [], []
                 if gopt.fused_seeds:
-                    rows, buf, n2 = _fused_seeds(cfg, states, jobs, chunk, cache, cplx)
+                    fuse = _fused_seeds_plan if cfg.ed_mode == "superc" else _fused_seeds
+                    rows, buf, n2 = fuse(cfg, states, jobs, chunk, cache, cplx)
                     keep = [q for q, v in enumerate(n2) if v != 0.0]    # norm2 == 0: no fraction
                     live, norms = [rows[q] for q in keep], [float(n2[q]) for q in keep]
                     if not live:
@@ -504,7 +658,7 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
                     if record is not None:
                         record.append((n, dict(channel=tag, isector=states.sectors[k], op=op, norm2=norms[q],
                                                alfa=a[q], beta=b[q], nlanc=int(nl[q]))))
-                    fracs[n] = (comp, _peso_bz(states, k, weight, norms[q], zeta), states.energies[k], E, z,
+                    fracs[n] = (comp, _peso(cfg)(states, k, weight, norms[q], zeta), states.energies[k], E, z,
                                 isign)
     finally:
         cache.close()
@@ -566,6 +720,92 @@ def _dist():
     return None
 
 
+def _with_broadcast_vectors(cfg, states, owners, device):
+    """The state list with every ordinary entry's vector on this rank
+    (farm_diag keeps them on their owner; a twin entry is rebuilt from its
+    partner on every rank)."""
+    dist = _dist()
+    if not dist or owners is None:
+        return states
+    from .farm import broadcast_vector
+
+    vecs = list(states.vectors)
+    for k, isec in enumerate(states.sectors):
+        if states.partner(k) is not None:     # a twin entry: every rank rebuilds it from the partner
+            continue
+        dim = setup_pointers(cfg)[isec - 1].dim
+        cplx = not cfg.is_real() or is_complex_vector(vecs[k])
+        flag = [cplx]
+        dist.broadcast_object_list(flag, src=owners[k])
+        vecs[k] = broadcast_vector(vecs[k], owners[k], dim, flag[0], device)
+    return states.with_vectors(vecs)
+
+
+def _sum_jobs(cfg, states, gopt, jobs, Gm, Gr, device, record, runner, who: str, ncomp: Optional[int] = None):
+    """Run this rank's share of `jobs` and add every continued fraction into
+    the host arrays Gm, Gr (indexed by a job's component), summed over the
+    ranks of the process group: the part of build_gf and build_gf_superc
+    between the job list and the recombination.  ncomp: the arrays are
+    (ncomp, L) and a component is a flat index."""
+    wm = matsubara(gopt.beta, gopt.Lmats)
+    wr = realaxis(gopt.wini, gopt.wfin, gopt.Lreal)
+    dist = _dist()
+    rank = dist.get_rank() if dist else 0
+    world = dist.get_world_size() if dist else 1
+    if world > 1:
+        from .farm import lpt_partition
+
+        costs = [float(min(j[5].dim, gopt.lanc_nGFiter)) * j[5].dim for j in jobs]
+        mine = set(lpt_partition(costs, world)[rank])
+    else:
+        mine = set(range(len(jobs)))
+    if states.finite_t and gopt.beta != states.beta:
+        raise ValueError(f"{who}: GFOptions.beta = {gopt.beta} but the state list was weighted at "
+                         f"beta = {states.beta}")
+    # zeta_function (ED_DIAG.f90:403-412): sum of exp(-beta (Ei - Egs)), state_list%size at T=0
+    zeta = states.zeta if states.finite_t else float(states.size)
+    todo = [n for n in range(len(jobs)) if n in mine]
+    poles = PoleSums(cfg.Nspin, cfg.Norb, wm, wr, gopt.eps, device, ncomp) if runner is None else None
+    if runner is None and gopt.batch:
+        rec = [] if record is not None else None
+        _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, rec)
+        if record is not None:
+            record.extend(r for _, r in sorted(rec, key=lambda t: t[0]))
+    elif runner is None and record is None and gopt.workers > 1 and len(todo) > 1:
+        _run_jobs_threaded(cfg, states, gopt, jobs, todo, device, poles, zeta)
+    else:
+        cache = _SectorCache(cfg, gopt, device)
+        try:
+            for n in todo:
+                job = jobs[n]
+                if runner is None:
+                    _run_job(cfg, states, gopt, job, cache, poles, record, zeta)
+                else:
+                    runner(cfg, states, gopt, job, wm, wr, Gm[job[0]], Gr[job[0]], zeta)
+        finally:
+            cache.close()
+    if poles is not None:
+        poles.flush()
+    if world > 1:
+        import torch
+
+        if poles is not None and dist.get_backend() == "nccl":
+            for t in (poles.Gm, poles.Gr):            # device G, summed over ranks in HBM
+                dist.all_reduce(torch.view_as_real(t))
+        elif poles is not None:
+            for t in (poles.Gm, poles.Gr):
+                h = torch.view_as_real(t).cpu()
+                dist.all_reduce(h)
+                torch.view_as_real(t).copy_(h)
+        else:
+            for G in (Gm, Gr):
+                t = torch.view_as_real(torch.from_numpy(G))   # (re, im) pairs: plain f64 sum
+                dist.all_reduce(t)
+                G[...] = torch.view_as_complex(t).numpy()
+    if poles is not None:
+        poles.to_host(Gm, Gr)
+
+
 def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None, device: int = 0,
              record: Optional[list] = None, owners: Optional[List[int]] = None, runner=None):
     """impGmats, impGreal (Nspin, Nspin, Norb, Norb, L) for ed_mode normal
@@ -599,84 +839,15 @@ def build_gf(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None,
     G_m, G_r, zeta)` replaces the device job (the CPU tests pass the oracle's)."""
     gopt = gopt or GFOptions()
     if cfg.ed_mode == "superc":
-        raise NotImplementedError("superc Green's function (ED_GF_SUPERC) is outside this hot path")
+        raise NotImplementedError("build_gf returns (Gmats, Greal) only: the superc Green's function "
+                                  "(ED_GF_SUPERC, G and the anomalous F) is build_gf_superc")
     No, Nsp = cfg.Norb, cfg.Nspin
-    wm = matsubara(gopt.beta, gopt.Lmats)
-    wr = realaxis(gopt.wini, gopt.wfin, gopt.Lreal)
     Gm = np.zeros((Nsp, Nsp, No, No, gopt.Lmats), dtype=np.complex128)
     Gr = np.zeros((Nsp, Nsp, No, No, gopt.Lreal), dtype=np.complex128)
-    dist = _dist()
-    rank = dist.get_rank() if dist else 0
-    world = dist.get_world_size() if dist else 1
-    if dist and owners is not None:
-        from .farm import broadcast_vector
-
-        vecs = list(states.vectors)
-        for k, isec in enumerate(states.sectors):
-            if states.partner(k) is not None:     # a twin entry: every rank rebuilds it from the partner
-                continue
-            dim = setup_pointers(cfg)[isec - 1].dim
-            cplx = not cfg.is_real() or is_complex_vector(vecs[k])
-            flag = [cplx]
-            dist.broadcast_object_list(flag, src=owners[k])
-            vecs[k] = broadcast_vector(vecs[k], owners[k], dim, flag[0], device)
-        states = states.with_vectors(vecs)
+    states = _with_broadcast_vectors(cfg, states, owners, device)
     jobs, pairs = _job_list(cfg, states, gopt.orbital_mix)
     opairs = orbital_pairs(cfg) if gopt.orbital_mix else []
-    if world > 1:
-        from .farm import lpt_partition
-
-        costs = [float(min(j[5].dim, gopt.lanc_nGFiter)) * j[5].dim for j in jobs]
-        mine = set(lpt_partition(costs, world)[rank])
-    else:
-        mine = set(range(len(jobs)))
-    if states.finite_t and gopt.beta != states.beta:
-        raise ValueError(f"build_gf: GFOptions.beta = {gopt.beta} but the state list was weighted at "
-                         f"beta = {states.beta}")
-    # zeta_function (ED_DIAG.f90:403-412): sum of exp(-beta (Ei - Egs)), state_list%size at T=0
-    zeta = states.zeta if states.finite_t else float(states.size)
-    todo = [n for n in range(len(jobs)) if n in mine]
-    poles = PoleSums(Nsp, No, wm, wr, gopt.eps, device) if runner is None else None
-    if runner is None and gopt.batch:
-        rec = [] if record is not None else None
-        _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, rec)
-        if record is not None:
-            record.extend(r for _, r in sorted(rec, key=lambda t: t[0]))
-    elif runner is None and record is None and gopt.workers > 1 and len(todo) > 1:
-        _run_jobs_threaded(cfg, states, gopt, jobs, todo, device, poles, zeta)
-    else:
-        cache = _SectorCache(cfg, gopt, device)
-        try:
-            for n in todo:
-                job = jobs[n]
-                ispin, jspin, iorb, jorb = job[0]
-                g_m, g_r = Gm[ispin, jspin, iorb, jorb], Gr[ispin, jspin, iorb, jorb]
-                if runner is None:
-                    _run_job(cfg, states, gopt, job, cache, poles, record, zeta)
-                else:
-                    runner(cfg, states, gopt, job, wm, wr, g_m, g_r, zeta)
-        finally:
-            cache.close()
-    if poles is not None:
-        poles.flush()
-    if world > 1:
-        import torch
-
-        if poles is not None and dist.get_backend() == "nccl":
-            for t in (poles.Gm, poles.Gr):            # device G, summed over ranks in HBM
-                dist.all_reduce(torch.view_as_real(t))
-        elif poles is not None:
-            for t in (poles.Gm, poles.Gr):
-                h = torch.view_as_real(t).cpu()
-                dist.all_reduce(h)
-                torch.view_as_real(t).copy_(h)
-        else:
-            for G in (Gm, Gr):
-                t = torch.view_as_real(torch.from_numpy(G))   # (re, im) pairs: plain f64 sum
-                dist.all_reduce(t)
-                G[...] = torch.view_as_complex(t).numpy()
-    if poles is not None:
-        poles.to_host(Gm, Gr)
+    _sum_jobs(cfg, states, gopt, jobs, Gm, Gr, device, record, runner, "build_gf")
     for ispin, jspin, iorb in pairs:               # build_gf_nonsu2 :35-48
         for G in (Gm, Gr):
             G[ispin, jspin, iorb, iorb] = 0.5 * (G[ispin, jspin, iorb, iorb]
@@ -703,3 +874,52 @@ def build_gf_normal(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] 
             ch = r["channel"]
             record.append(dict(r, ispin=ch[1], iorb=ch[2], jorb=ch[3] if ch[0] == "orbmix" else ch[2]))
     return Gm, Gr
+
+
+def build_gf_superc(cfg: EDConfig, states: StateList, gopt: Optional[GFOptions] = None, device: int = 0,
+                    record: Optional[list] = None, owners: Optional[List[int]] = None, runner=None):
+    """impGmats, impGreal, impFmats, impFreal, each (1, 1, Norb, Norb, L), for
+    ed_mode superc: build_gf_superc / lanc_build_gf_superc_c /
+    add_to_lanczos_gf_superc (ED_GF_SUPERC.f90:18-77, 88-446, 757-803).
+
+    Per orbital a and kept state |n> six seeds go into three aux channels
+    (`_job_list_superc`): G_aa from c+_{a,up}|n> and c_{a,up}|n>, barG_aa
+    from c_{a,dw}|n> and c+_{a,dw}|n>, A_aa from (c+_{a,up} + c_{a,dw})|n> and
+    (c_{a,up} + c+_{a,dw})|n>; the first of each pair lives in sector sz+1 with
+    isign +1, the second in sz-1 with isign -1.  The weight is `_peso_superc`
+    (no beta dE < 200 cut, unlike the normal mode).  After the all-reduce over
+    the aux arrays (ED_GF_SUPERC.f90:39-44)
+      G[0,0,a,a] = G_aa,   F[0,0,a,a] = 0.5 * (A_aa - G_aa - barG_aa).
+
+    Orbital off-diagonal entries [0,0,a,b], a != b, stay zero, also for a
+    hybrid bath: the reference's pair loop (lanc_build_gf_superc_mix_c,
+    ED_GF_SUPERC.f90:455-738) accumulates on aux arrays it does not zero
+    between pairs (ED_GF_SUPERC.f90:31-33 is the only reset, ED_GF_SUPERC.f90:55-65 the pair loop), stores that raw
+    sum as impGmats(a,b) and never fills (b,a), so there is no sound value to
+    reproduce.
+
+    The host paths (serial, threaded, batched, gopt.fused_seeds with
+    ed_sector_seed_plan), the rank split, `owners`, `record`, finite-temperature
+    and twin lists and `runner` are build_gf's; a record entry's channel is
+    ("superc", aux channel 0..2, iorb)."""
+    gopt = gopt or GFOptions()
+    if cfg.ed_mode != "superc":
+        raise ValueError("build_gf_superc needs ed_mode='superc'")
+    No = cfg.Norb
+    aux_m = np.zeros((SUPERC_CHANNELS * No, gopt.Lmats), dtype=np.complex128)
+    aux_r = np.zeros((SUPERC_CHANNELS * No, gopt.Lreal), dtype=np.complex128)
+    states = _with_broadcast_vectors(cfg, states, owners, device)
+    jobs = _job_list_superc(cfg, states)
+    _sum_jobs(cfg, states, gopt, jobs, aux_m, aux_r, device, record, runner, "build_gf_superc",
+              ncomp=SUPERC_CHANNELS * No)
+    out = []
+    for aux in (aux_m, aux_r):
+        G = np.zeros((1, 1, No, No, aux.shape[1]), dtype=np.complex128)
+        F = np.zeros_like(G)
+        for a in range(No):
+            g, gbar, A = aux[SUPERC_CHANNELS * a:SUPERC_CHANNELS * (a + 1)]
+            G[0, 0, a, a] = g
+            F[0, 0, a, a] = 0.5 * (A - g - gbar)
+        out.append((G, F))
+    (Gm, Fm), (Gr, Fr) = out
+    return Gm, Gr, Fm, Fr

@@ -41,6 +41,8 @@
  *                                 get_twin_sector ED_SETUP.f90:1196-1212)
  *   ed_sector_seed_batch      <- the vvinit loops of lanc_build_gf_normal_c / _mix_c
  *                                ED_GF_NORMAL.f90:159-174, ED_GF_NORMAL.f90:312-344
+ *   ed_sector_seed_plan       <- the six vvinit loops of lanc_build_gf_superc_c
+ *                                ED_GF_SUPERC.f90:119-439
  */
 #ifndef ED_GPU_H
 #define ED_GPU_H
@@ -352,6 +354,25 @@ int ed_sector_seed_batch(const ed_sector* src, const ed_sector* dst, int32_t op,
                          int32_t nseed, const double* coef,
                          int32_t vtype, const void* src_vec,
                          void* seeds, double* norm2, void* stream);
+/* The same for a group whose images mix operator types: the superconducting
+ * seeds of lanc_build_gf_superc_c, ED_GF_SUPERC.f90:119-166 (c^+_up),
+ * ED_GF_SUPERC.f90:219-268 (c_dw) and ED_GF_SUPERC.f90:320-378 (their sum)
+ * into sz+1, ED_GF_SUPERC.f90:168-217, ED_GF_SUPERC.f90:270-318 and
+ * ED_GF_SUPERC.f90:380-439 into sz-1.  Image l is ops[l] (0: c, 1: c^+) on
+ * the 0-based bit levels[l] of |src_vec>; seed s is image terms[2s], or image
+ * terms[2s] + image terms[2s+1] (a negative second index: the first alone),
+ * with unit coefficients, normalised; for a pair that is the arithmetic of
+ * ed_sector_apply_op + ed_sector_apply_op_acc(coef = 1).  ED_ERR_ARG, before
+ * anything is launched, unless 1 <= nlev <= 2*ED_MAX_NORB, 1 <= nseed <= 32,
+ * every image maps src into dst (as ed_sector_apply_op), the (level, op) pairs
+ * are distinct, every index is below nlev and the two of a seed differ, and
+ * vtype is 0 or 1.  seeds, norm2, determinism, row-split sectors and
+ * synchronisation as ed_sector_seed_batch. */
+int ed_sector_seed_plan(const ed_sector* src, const ed_sector* dst,
+                        int32_t nlev, const int32_t* levels, const int32_t* ops,
+                        int32_t nseed, const int32_t* terms,
+                        int32_t vtype, const void* src_vec,
+                        void* seeds, double* norm2, void* stream);
 /* Vector of a twin entry of the state list (es_return_cvector,
  * ED_EIGENSPACE.f90:414-445; twin_sector_order and flip_state,
  * ED_SETUP.f90:1123-1186), from its partner's vector:
