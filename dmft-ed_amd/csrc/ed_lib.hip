@@ -3523,6 +3523,27 @@ int ed_sector_lanc_mode(ed_sector* s, int32_t vtype, int32_t path) {
   return persist_mode(s, vtype ? 1 : 0, resolve_path(s, path));
 }
 
+// The k_lanc_persist instantiation behind that mode: the template values
+// persist_launch (ed_persist_launch.hpp) dispatches on, read from the fields
+// persist_mode() and persist_geom() hold.  Nothing is chosen here.
+int ed_sector_lanc_geom(ed_sector* s, int32_t vtype, int32_t path, int32_t geom[6]) {
+  if (!s || !geom) return fail(ED_ERR_ARG, "null");
+  const int vc = vtype ? 1 : 0;
+  if (vc == 0 && s->hc) return fail(ED_ERR_ARG, "complex H needs vtype=1");
+  HIPCK(hipSetDevice(s->device));
+  const int mode = persist_mode(s, vc, resolve_path(s, path));
+  const PersistGeom g = persist_geom(s);
+  for (int k = 0; k < 6; k++) geom[k] = 0;
+  geom[0] = mode;
+  geom[5] = s->hc ? 1 : 0;
+  if (mode < 0) return ED_OK;
+  geom[1] = mode >= 2 ? kPRegBlock : kPBlock;
+  geom[2] = mode == 2 ? g.preg_rpt : mode == 3 ? g.kreg_rpt : mode == 4 ? g.pkr_rpt : persist_rpt01(g.dim);
+  geom[3] = mode == 2 ? g.preg_E : mode == 3 ? g.kreg_W : mode == 4 ? g.pkr_E : 1;
+  geom[4] = (int32_t)s->pchoice.lds;
+  return ED_OK;
+}
+
 int ed_sector_eigh(ed_sector* s, int32_t vtype, int32_t nev, int32_t ncv, int32_t maxit,
                               double tol, const void* v0, double* evals, void* evecs, int32_t* nconv,
                               int32_t* nhv) {

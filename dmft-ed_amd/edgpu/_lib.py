@@ -50,6 +50,7 @@ SIGNATURES = {
     "ed_sector_lanc_eigh": ([_P, _i32, _P, _i32, _f64, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_lanc_run": ([_P, _i32, _P, _i32, _P, _P, _P, _P], ctypes.c_int),
     "ed_sector_lanc_mode": ([_P, _i32, _i32], ctypes.c_int),
+    "ed_sector_lanc_geom": ([_P, _i32, _i32, _P], ctypes.c_int),
     "ed_gpu_eigh": ([_i32, _i32, _i32, _f64, _P, _P, _P, _P], ctypes.c_int),
     "ed_sector_kron_rows": ([_P, _i32, _i64, _i64, _P, _P, _P], ctypes.c_int),
     "ed_sector_kron_cols": ([_P, _i32, _i64, _i64, _P, _P, _i32, _P], ctypes.c_int),

@@ -235,6 +235,17 @@ class Sector:
         vt, _ = self._vec_arg(None, real)
         return int(_lib.load().ed_sector_lanc_mode(self._h, vt, path))
 
+    def lanc_geom(self, real: Optional[bool] = None, path: int = -1) -> dict:
+        """Launch form of that recurrence (ed_sector_lanc_geom): mode, threads
+        of the workgroup, the kernel's template RPT and width (W for modes
+        2/3, E for mode 4, 1 for modes 0/1), dynamic LDS bytes, and hc (H held
+        as complex(8)).  mode -1: multi-kernel, the other numbers are 0."""
+        vt, _ = self._vec_arg(None, real)
+        g = np.zeros(6, dtype=np.int32)
+        check(_lib.load().ed_sector_lanc_geom(self._h, vt, path, _ptr(g)), "ed_sector_lanc_geom")
+        return dict(mode=int(g[0]), threads=int(g[1]), rpt=int(g[2]), width=int(g[3]), lds=int(g[4]),
+                    hc=bool(g[5]))
+
     def eigh(self, neigen: int = 6, ncv: int = 23, maxit: int = 512, tol: float = 1e-12,
              v0: Optional[np.ndarray] = None, vectors: bool = True, real: Optional[bool] = None,
              on_device: bool = False):

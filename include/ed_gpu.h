@@ -268,6 +268,19 @@ int ed_sector_lanc_eigh(ed_sector* s, int32_t vtype, const void* v0, int32_t nit
  * register layout) or -1 (graph-captured multi-kernel), under the sector's
  * ED_OPT_* options. */
 int ed_sector_lanc_mode(ed_sector* s, int32_t vtype, int32_t path);
+/* Diagnostic: the launch form of that recurrence, i.e. the k_lanc_persist
+ * instantiation a run with (vtype, path) would start under the sector's
+ * ED_OPT_* options.  Read-only: it reports what ed_sector_lanc_mode derives
+ * (and caches) and chooses nothing of its own.
+ *   geom[0]  mode as ed_sector_lanc_mode (-1: multi-kernel; geom[1..4] = 0)
+ *   geom[1]  threads of the workgroup (1024 for modes 0/1, 512 for 2/3/4)
+ *   geom[2]  template RPT, the row slots per thread
+ *   geom[3]  template width: ELL row width W (modes 2/3), hop-list width E
+ *            (mode 4), 1 for modes 0/1
+ *   geom[4]  dynamic LDS bytes of the launch
+ *   geom[5]  1 when H is held as complex(8) (HC forms), 0 when as real(8)
+ * vtype 0 on a complex H is ED_ERR_ARG, as for the Lanczos entry points. */
+int ed_sector_lanc_geom(ed_sector* s, int32_t vtype, int32_t path, int32_t geom[6]);
 /* Lowest `nev` eigenpairs by thick-restart Lanczos with full (CGS2)
  * reorthogonalisation, Krylov basis of `ncv` vectors resident in HBM: the
  * device replacement of SciFortran's ARPACK sp_eigh (ED_DIAG.f90:145-167,

@@ -64,8 +64,8 @@ def hybrid():
     return cfg
 
 
-def replica_cplx():
-    cfg = EDConfig(Norb=2, Nbath=2, Nspin=1, bath_type="replica", Uloc=(2.0, 1.0, 0.0),
+def replica_cplx(Nbath=2):
+    cfg = EDConfig(Norb=2, Nbath=Nbath, Nspin=1, bath_type="replica", Uloc=(2.0, 1.0, 0.0),
                    Ust=0.8, Jh=0.2)
     cfg.impHloc = _hloc(1, 2, 8, cplx=True)
     b = init_dmft_bath(cfg)
@@ -96,8 +96,8 @@ def nonsu2_rand():
     return cfg
 
 
-def nonsu2_replica():
-    cfg = EDConfig(Norb=1, Nbath=3, Nspin=2, ed_mode="nonsu2", bath_type="replica")
+def nonsu2_replica(Nbath=3):
+    cfg = EDConfig(Norb=1, Nbath=Nbath, Nspin=2, ed_mode="nonsu2", bath_type="replica")
     cfg.impHloc = _hloc(2, 1, 12, cplx=True, spinflip=True)
     b = init_dmft_bath(cfg)
     rng = np.random.default_rng(14)

@@ -26,6 +26,33 @@ def _e0_scipy(csr, dim):
     return float(sla.eigsh(A, k=1, which="SA", tol=1e-14)[0][0])
 
 
+# The recurrence each leg of test_tridiag_and_ground_state runs on sectors[0]
+# (complex H, complex vectors): Sector.lanc_mode of the (stored, matrix-free)
+# sector per leg; -1 = the graph-captured multi-kernel recurrence.  The
+# register modes take at most 80 ELL words per thread here (preg_cap), so
+# c5 (7,0) (14 x 8), normal_rand (4,4) (14 x 10) and nonsu2_rand (6,0)
+# (longest row 21 > 16) have no MODE 2; MODE 4 needs a real H; the
+# matrix-free modes 1 and 3 need the Kronecker form (normal mode without
+# Jx / Jp).  Every launch form by name: tests/persist_shape_cases.py.
+_M = -1
+LANC_MODE = {
+    #                 default    persist_stored  no_preg   no_persist
+    "c2":             ((2, 3),   (0, 3),         (_M, 1),  (_M, _M)),
+    "c5":             ((_M, _M), (0, _M),        (_M, _M), (_M, _M)),
+    "normal_rand":    ((_M, 1),  (0, 1),         (_M, 1),  (_M, _M)),
+    "normal_jh":      ((2, _M),  (0, _M),        (_M, _M), (_M, _M)),
+    "normal_3orb":    ((2, _M),  (0, _M),        (_M, _M), (_M, _M)),
+    "hybrid":         ((2, 3),   (0, 3),         (_M, 1),  (_M, _M)),
+    "replica_cplx":   ((2, 3),   (0, 3),         (_M, 1),  (_M, _M)),
+    "nonsu2_rand":    ((_M, _M), (0, _M),        (_M, _M), (_M, _M)),
+    "nonsu2_replica": ((2, _M),  (0, _M),        (_M, _M), (_M, _M)),
+    "nonsu2_jz":      ((2, _M),  (0, _M),        (_M, _M), (_M, _M)),
+    "superc":         ((2, _M),  (0, _M),        (_M, _M), (_M, _M)),
+    "superc_2orb":    ((2, _M),  (0, _M),        (_M, _M), (_M, _M)),
+}
+_LEGS = ["default", "l2", "lds", "multi"]
+
+
 @pytest.mark.parametrize("persist", ["default", "l2", "lds", "multi"],
                          ids=["persistent", "persist_l2", "persist_lds", "multikernel"])
 @pytest.mark.parametrize("name,factory,sectors", CASES, ids=[c[0] for c in CASES])
@@ -50,6 +77,7 @@ def test_tridiag_and_ground_state(name, factory, sectors, persist):
     ar, br, nr = lanc_tridiag(csr, v0, n)
     for direct in (False, True):
         with Sector(cfg, q1, q2, stored=not direct, direct=direct, options=opts) as S:
+            assert S.lanc_mode() == LANC_MODE[name][_LEGS.index(persist)][int(direct)]
             a, b, ng = S.lanc_tridiag(v0, n)
             assert ng == nr
             k = min(15, nr)
