@@ -7,6 +7,7 @@
 #include "ed_obs.hpp"
 #include "ed_twin.hpp"
 #include "ed_seed.hpp"
+#include "ed_chi.hpp"
 
 using namespace edg;
 
@@ -590,6 +591,58 @@ int ed_sector_seed_plan(const ed_sector* src, const ed_sector* dst, int32_t nlev
   } else {
     hipLaunchKernelGGL(k_seed_plan<false>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
                        (const double*)src_vec, (double*)seeds, part);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
+  }
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
+  return ED_OK;
+}
+
+// Seeds of operators diagonal in the Fock basis (ed_chi.hpp): the vvinit loops
+// of lanc_ed_build_spinChi_c (ED_GF_CHISPIN.f90:98-103), _tot_c
+// (ED_GF_CHISPIN.f90:194-199) and of the density builders
+// (ED_GF_CHIDENS.f90:127-132) for every operator of one kept state, with their
+// dot_product and divide.  The seed stays in s; every check comes before the
+// first launch: a refused call leaves `seeds` untouched.
+int ed_sector_seed_diag(const ed_sector* s, int32_t nlev, const int32_t* levels, int32_t nseed,
+                        const double* weight, int32_t vtype, const void* src_vec, void* seeds, double* norm2,
+                        void* stream) {
+  if (!s || !levels || !weight || !src_vec || !seeds || !norm2) return fail(ED_ERR_ARG, "null");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (nlev < 1 || nlev > kDiagMaxLev) return fail(ED_ERR_ARG, "nlev must be 1..2*ED_MAX_NORB");
+  if (nseed < 1 || nseed > kDiagMaxSeeds) return fail(ED_ERR_ARG, "nseed must be 1..32");
+  DiagTable T;
+  if (seed_diag_compile(s->Mh.ns, nlev, levels, nseed, weight, &T) != ED_OK)
+    return fail(ED_ERR_ARG, "seed table: levels must be distinct and below 2*Ns");
+  const size_t vs = vtype ? 16 : 8;
+  {
+    const uintptr_t a = (uintptr_t)src_vec, b = (uintptr_t)seeds;
+    if (a < b + (size_t)nseed * s->dim * vs && b < a + (size_t)s->dim * vs)
+      return fail(ED_ERR_ARG, "seeds overlaps src_vec");
+  }
+  CK(whole_only(s));
+  HIPCK(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t dim = s->dim;
+  const int g = std::min(grid_for(dim), kSeedMaxGrid);
+  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
+  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
+  DevFree fr{part, st};
+  PinnedLease pin((size_t)nseed * sizeof(double), st);
+  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
+  double* dn = part + (size_t)nseed * g;
+  double* hn = (double*)pin.p;
+  if (vtype) {
+    hipLaunchKernelGGL(k_seed_diag<true>, dim3(g), dim3(kBlock), 0, st, s->d_map, dim, T, (const double2*)src_vec,
+                       (double2*)seeds, part);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
+  } else {
+    hipLaunchKernelGGL(k_seed_diag<false>, dim3(g), dim3(kBlock), 0, st, s->d_map, dim, T, (const double*)src_vec,
+                       (double*)seeds, part);
     HIPCK(hipGetLastError());
     hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
   }

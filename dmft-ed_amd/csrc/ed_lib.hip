@@ -16,6 +16,7 @@
 #include "ed_trlbatch.hpp"
 #include "ed_trlmulti.hpp"
 #include "ed_hosteig.hpp"
+#include "ed_chi.hpp"
 
 using namespace edg;
 
@@ -3312,6 +3313,60 @@ int ed_gf_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const 
   hipLaunchKernelGGL(k_gf_poles, dim3((nt + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const GfFrac*)db, nfrac,
                      (const double*)(db + bf), (const double*)(db + bf + be), wm, lmats, wr, lreal, eps,
                      (double2*)gm, (double2*)gr);
+  const hipError_t le = hipGetLastError();
+  (void)hipFreeAsync(d, st);
+  // the host staging vector dies on return: the copy must have completed
+  HIPCK(hipStreamSynchronize(st));
+  HIPCK(le);
+  return ED_OK;
+}
+
+// Pole sums of the susceptibilities (k_chi_poles, ed_chi.hpp): every fraction
+// is one tridiagonalisation of add_to_lanczos_spinChi (ED_GF_CHISPIN.f90:254-323)
+// with both isign calls.  The thermal factors of a pole are computed here
+// (chi_thermal: expm1), so the kernel's only transcendental is exp on tau.
+int ed_chi_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const double* z, const double* peso,
+                     const double* Ei, const int32_t* comp, double beta, const double* vm, int32_t lmats,
+                     const double* tau, int32_t ltau, const double* wr, int32_t lreal, double eps, double* chi_iv,
+                     double* chi_tau, double* chi_w, void* stream) {
+  if (nfrac < 0 || lmats < 0 || ltau < 0 || lreal < 0) return fail(ED_ERR_ARG, "bad sizes");
+  if (nfrac == 0) return ED_OK;
+  if (!npole || !E || !z || !peso || !Ei || !comp || !vm || !tau || !chi_iv || !chi_tau || (lreal && (!wr || !chi_w)))
+    return fail(ED_ERR_ARG, "null");
+  std::vector<ChiFrac> fr(nfrac);
+  int64_t np = 0;
+  for (int f = 0; f < nfrac; f++) {
+    if (npole[f] < 0 || comp[f] < 0) return fail(ED_ERR_ARG, "bad fraction");
+    fr[f].p0 = (int32_t)np;
+    fr[f].np = npole[f];
+    fr[f].comp = comp[f];
+    fr[f].pad = 0;
+    fr[f].peso = peso[f];
+    fr[f].ei = Ei[f];
+    np += npole[f];
+  }
+  // one staging buffer: fractions | E | z | 1 - exp(-beta D) | s(D)
+  const size_t bf = fr.size() * sizeof(ChiFrac), be = (size_t)std::max<int64_t>(np, 1) * 8;
+  std::vector<unsigned char> hb(bf + 4 * be);
+  memcpy(hb.data(), fr.data(), bf);
+  if (np) {
+    memcpy(hb.data() + bf, E, np * 8);
+    memcpy(hb.data() + bf + be, z, np * 8);
+    double* hf = (double*)(hb.data() + bf + 2 * be);
+    double* hs = (double*)(hb.data() + bf + 3 * be);
+    for (int f = 0; f < nfrac; f++)
+      for (int j = fr[f].p0; j < fr[f].p0 + fr[f].np; j++) chi_thermal(beta, E[j] - fr[f].ei, hf + j, hs + j);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  void* d = nullptr;
+  HIPCK(hipMallocAsync(&d, hb.size(), st));
+  HIPCK(hipMemcpyAsync(d, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
+  const unsigned char* db = (const unsigned char*)d;
+  const int nt = (lmats + 1) + (ltau + 1) + lreal;
+  hipLaunchKernelGGL(k_chi_poles, dim3((nt + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const ChiFrac*)db, nfrac,
+                     (const double*)(db + bf), (const double*)(db + bf + be), (const double*)(db + bf + 2 * be),
+                     (const double*)(db + bf + 3 * be), beta, vm, lmats + 1, tau, ltau + 1, wr, lreal, eps,
+                     (double2*)chi_iv, chi_tau, (double2*)chi_w);
   const hipError_t le = hipGetLastError();
   (void)hipFreeAsync(d, st);
   // the host staging vector dies on return: the copy must have completed

@@ -9,6 +9,8 @@ Modules:
   diag        ed_diag sector loop (single GPU) and the T=0 state list
   farm        sector farm over ranks (torch.distributed / RCCL)
   gf          Green's functions (normal, nonSU2): device seeds, Lanczos, poles
+  chi         spin and density susceptibilities of the kept states: diagonal
+              seeds (Sector.seed_diag), Lanczos, bosonic / tau / real-axis poles
   observables impurity observables and local energies of the kept states
               (observables_impurity / local_energy_impurity) from device
               vectors: Sector.nn_moments / Sector.expect
@@ -19,5 +21,7 @@ first use and its absence is an error (no CPU fallback).
 """
 from .params import EDConfig, make_config, init_dmft_bath, random_bath  # noqa: F401
 from .sectors import setup_pointers  # noqa: F401
+from .chi import Chi, ChiOptions, build_chi  # noqa: F401
 
-__all__ = ["EDConfig", "make_config", "init_dmft_bath", "random_bath", "setup_pointers"]
+__all__ = ["EDConfig", "make_config", "init_dmft_bath", "random_bath", "setup_pointers", "Chi", "ChiOptions",
+           "build_chi"]

@@ -320,6 +320,27 @@ class Sector:
                                            _ptr(out), _stream_ptr(st)), "ed_sector_expect")
         return out[0::2] + 1j * out[1::2]
 
+    # ------------------------------------------------- susceptibility seeds
+    def seed_diag(self, vec, levels, weights, out=None):
+        """Seeds of operators diagonal in the Fock basis (ed_sector_seed_diag):
+        seeds[q][r] = (sum_l weights[q][l] * bit(map[r], levels[l])) * vec[r],
+        normalised, for a state vector of this sector; the vvinit loops of
+        the susceptibility builders (ED_GF_CHISPIN.f90:98-103,
+        ED_GF_CHIDENS.f90:127-132).  Returns (device tensor (nseed, dim) of the
+        vector's type, norm2 (nseed,)); a seed with norm2 == 0 is all zero.
+        out: a contiguous device tensor of that shape and type to write into."""
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1, len(lv))
+        vt, x, st = self._state_arg(vec)
+        if out is None:
+            out = self._out_array((w.shape[0], self.dim), vt, True)
+        elif tuple(out.shape) != (w.shape[0], self.dim) or out.dtype != x.dtype or not out.is_contiguous():
+            raise ValueError("seed_diag: out must be a contiguous (nseed, dim) tensor of the vector's type")
+        n2 = np.zeros(w.shape[0])
+        check(_lib.load().ed_sector_seed_diag(self._h, len(lv), _ptr(lv), w.shape[0], _ptr(w), vt, _tptr(x),
+                                              _tptr(out), _ptr(n2), _stream_ptr(st)), "ed_sector_seed_diag")
+        return out, n2
+
     # ---------------------------------------------------------- twin sectors
     def twin_vector(self, dst: "Sector", vec):
         """The vector of a twin entry of the state list (es_return_cvector,

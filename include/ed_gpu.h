@@ -386,6 +386,25 @@ int ed_sector_seed_plan(const ed_sector* src, const ed_sector* dst,
                         int32_t nseed, const int32_t* terms,
                         int32_t vtype, const void* src_vec,
                         void* seeds, double* norm2, void* stream);
+/* Seeds of operators diagonal in the Fock basis, every one of a kept state in
+ * one pass: the vvinit loops of the susceptibility builders
+ * (ED_GF_CHISPIN.f90:98-103, ED_GF_CHISPIN.f90:194-199,
+ * ED_GF_CHIDENS.f90:127-132) with their dot_product and divide.  Seed q is
+ *   seeds[q][r] = (sum_l weight[q][l] * bit(map[r], levels[l])) * src_vec[r],
+ * the sum in level order in double, then normalised; norm2[q] = <seed|seed>
+ * before normalisation; a seed with norm2 == 0 is left all zero.  The seed
+ * stays in the sector of src_vec: any whole sector, stored or direct, of any
+ * ed_mode and of the Jz basis.  ED_ERR_ARG, before anything is launched,
+ * unless 1 <= nlev <= 2*ED_MAX_NORB, the levels are distinct 0-based bits
+ * below 2*Ns, 1 <= nseed <= 32, vtype is 0 or 1 and seeds does not overlap
+ * src_vec.  weight: [nseed][nlev] real, host.  seeds: device, [nseed][dim],
+ * written whole (no memset needed).  The norms are summed in a fixed order:
+ * two calls on the same input return the same bits.  Row-split sectors:
+ * ED_ERR_UNSUPPORTED.  Synchronous on `stream` (norm2 is a host result). */
+int ed_sector_seed_diag(const ed_sector* s, int32_t nlev, const int32_t* levels,
+                        int32_t nseed, const double* weight,
+                        int32_t vtype, const void* src_vec,
+                        void* seeds, double* norm2, void* stream);
 /* Vector of a twin entry of the state list (es_return_cvector,
  * ED_EIGENSPACE.f90:414-445; twin_sector_order and flip_state,
  * ED_SETUP.f90:1123-1186), from its partner's vector:
@@ -463,6 +482,25 @@ int ed_tridiag_poles(int32_t n, const double* alfa, const double* beta, double* 
 int ed_gf_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const double* z, const double* peso_bz,
                     const double* Ei, const int32_t* isign, const int32_t* comp, const double* wm, int32_t lmats,
                     const double* wr, int32_t lreal, double eps, double* gm, double* gr, void* stream);
+/* Pole sums of nfrac tridiagonalisations into device-resident
+ * susceptibilities, in list order: add_to_lanczos_spinChi
+ * (ED_GF_CHISPIN.f90:254-323) called with isign = +1 and then -1.  Fraction f
+ * has npole[f] poles (E, z = Z(1,j): concatenated, host), real weight peso[f]
+ * (the state's weight times norm2), energy Ei[f] and target component
+ * comp[f].  With D = E_j - Ei, p_j = (peso*z_j)*z_j and f_j = 1 - exp(-beta D)
+ * = -expm1(-beta D):
+ *   chi_iv[comp][0]  += 2 p_j s_j,   s_j = f_j / D, beta at D == 0
+ *   chi_iv[comp][i]  += p_j f_j [1/(i vm[i] + D) - 1/(i vm[i] - D)],  i = 1..lmats
+ *   chi_tau[comp][i] += p_j [exp(-tau[i] D) + exp(-(beta - tau[i]) D)],  i = 0..ltau
+ *   chi_w[comp][i]   += p_j f_j [1/(wr[i] + i eps + D) - 1/(wr[i] + i eps - D)]
+ * every -D term of a fraction pole by pole first, then every +D term (the
+ * reference's addition order).  chi_iv (ncomp x (lmats+1)) and chi_w (ncomp x
+ * lreal): complex(8) device arrays; chi_tau (ncomp x (ltau+1)): real(8);
+ * vm[lmats+1], tau[ltau+1], wr[lreal]: device.  Synchronous on `stream`. */
+int ed_chi_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const double* z, const double* peso,
+                     const double* Ei, const int32_t* comp, double beta, const double* vm, int32_t lmats,
+                     const double* tau, int32_t ltau, const double* wr, int32_t lreal, double eps, double* chi_iv,
+                     double* chi_tau, double* chi_w, void* stream);
 
 /* ------------------------------------------------------ reference-style API */
 int ed_gpu_init(const ed_params* p);          /* ed_init_solver parameter hand-over */
