@@ -17,6 +17,8 @@
 //   seed_diag_host     the kernel's arithmetic, serially in row order.
 //   chi_thermal        1 - exp(-beta D) and s(D) = (1 - exp(-beta D)) / D of a
 //                      pole, by expm1 (departure 1).
+//   kChiBoth / kChiPlus / kChiMinus
+//                      the isign branches a fraction of the pole sum takes.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -91,6 +93,11 @@ inline void seed_diag_host(const DiagTable& T, int64_t dim, const uint32_t* map,
     }
   }
 }
+
+// Which isign branches of add_to_lanczos_spinChi a fraction takes: the value
+// is the isign argument of ed_chi_add_poles_signed (0: +1 and then -1).
+constexpr int32_t kChiBoth = 0, kChiPlus = 1, kChiMinus = -1;
+inline bool chi_sel_valid(int32_t isign) { return isign == kChiBoth || isign == kChiPlus || isign == kChiMinus; }
 
 // f = 1 - exp(-beta D) and s = f / D, with s(0) = beta exactly: -expm1(-x)
 // keeps every digit of f for small |x| and is right for D < 0, where the

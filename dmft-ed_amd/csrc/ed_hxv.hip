@@ -653,6 +653,70 @@ int ed_sector_seed_diag(const ed_sector* s, int32_t nlev, const int32_t* levels,
   return ED_OK;
 }
 
+// Seeds whose images are products of two ladder operators (ed_chi.hpp,
+// ed_seed_pair.hpp): the vvinit loops of the pair susceptibility
+// (ED_GF_CHIPAIR.f90:98-102, :144-148) and of lanc_ed_build_densChi_mix_c
+// (ED_GF_CHIDENS.f90:523-586, :596-659) for every operator of one kept state,
+// with their dot_product and divide.  src == dst is allowed (the inter-orbital
+// seeds stay in the kept state's sector).  Every check comes before the first
+// launch: a refused call leaves `seeds` untouched.
+int ed_sector_seed_pair(const ed_sector* src, const ed_sector* dst, int32_t nimg, const int32_t* images,
+                        int32_t nseed, const int32_t* terms, int32_t vtype, const void* src_vec, void* seeds,
+                        double* norm2, void* stream) {
+  if (!src || !dst || !images || !terms || !src_vec || !seeds || !norm2) return fail(ED_ERR_ARG, "null");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (nimg < 1 || nimg > kPairMaxImg) return fail(ED_ERR_ARG, "nimg must be 1..12");
+  if (nseed < 1 || nseed > kPairMaxSeeds) return fail(ED_ERR_ARG, "nseed must be 1..12");
+  if (src->device != dst->device) return fail(ED_ERR_ARG, "sectors on different devices");
+  {
+    const EdModel &a = src->Mh, &b = dst->Mh;
+    if (a.ns != b.ns || a.norb != b.norb || a.nbath != b.nbath || a.nspin != b.nspin || a.mode != b.mode ||
+        a.bath != b.bath || a.jz != b.jz)
+      return fail(ED_ERR_ARG, "sectors of different models");
+  }
+  // the kernel's index tables do not bounds-check: every image must map src into dst
+  PairPlan P;
+  if (seed_pair_compile(seed_sectors(src, dst), nimg, images, nseed, terms, &P) != ED_OK)
+    return fail(ED_ERR_ARG, "seed pair plan: lev1 != lev2, every image maps src into dst, images distinct, "
+                            "p and q below nimg, p != q");
+  const size_t vs = vtype ? 16 : 8;
+  {
+    const uintptr_t a = (uintptr_t)src_vec, b = (uintptr_t)seeds;
+    if (a < b + (size_t)nseed * dst->dim * vs && b < a + (size_t)src->dim * vs)
+      return fail(ED_ERR_ARG, "seeds overlaps src_vec");
+  }
+  CK(whole_only(src));
+  CK(whole_only(dst));
+  HIPCK(hipSetDevice(src->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t dim = dst->dim;
+  const int g = std::min(grid_for(dim), kSeedMaxGrid);
+  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
+  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
+  DevFree fr{part, st};
+  PinnedLease pin((size_t)nseed * sizeof(double), st);
+  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
+  double* dn = part + (size_t)nseed * g;
+  double* hn = (double*)pin.p;
+  const DevIndex idx{src->d_off, src->d_rank, src->T.ns, src->T.nst - 1};
+  if (vtype) {
+    hipLaunchKernelGGL(k_seed_pair<true>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
+                       (const double2*)src_vec, (double2*)seeds, part);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
+  } else {
+    hipLaunchKernelGGL(k_seed_pair<false>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
+                       (const double*)src_vec, (double*)seeds, part);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
+  }
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
+  return ED_OK;
+}
+
 // ------------------------------------------------ twin-sector vectors
 // (ed_twin.hpp).  get_twin_sector (ED_SETUP.f90:1196-1212): (nup, ndw) ->
 // (ndw, nup), sz -> -sz, n -> 2*Ns - n; it knows no (n, twoJz) sectors.

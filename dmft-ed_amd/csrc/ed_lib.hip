@@ -3323,12 +3323,14 @@ int ed_gf_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const 
 
 // Pole sums of the susceptibilities (k_chi_poles, ed_chi.hpp): every fraction
 // is one tridiagonalisation of add_to_lanczos_spinChi (ED_GF_CHISPIN.f90:254-323)
-// with both isign calls.  The thermal factors of a pole are computed here
+// with both isign calls (isign[f] == 0 or isign == NULL) or with the one named
+// by isign[f] = +-1.  The thermal factors of a pole are computed here
 // (chi_thermal: expm1), so the kernel's only transcendental is exp on tau.
-int ed_chi_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const double* z, const double* peso,
-                     const double* Ei, const int32_t* comp, double beta, const double* vm, int32_t lmats,
-                     const double* tau, int32_t ltau, const double* wr, int32_t lreal, double eps, double* chi_iv,
-                     double* chi_tau, double* chi_w, void* stream) {
+int ed_chi_add_poles_signed(int32_t nfrac, const int32_t* npole, const double* E, const double* z,
+                            const double* peso, const double* Ei, const int32_t* comp, const int32_t* isign,
+                            double beta, const double* vm, int32_t lmats, const double* tau, int32_t ltau,
+                            const double* wr, int32_t lreal, double eps, double* chi_iv, double* chi_tau,
+                            double* chi_w, void* stream) {
   if (nfrac < 0 || lmats < 0 || ltau < 0 || lreal < 0) return fail(ED_ERR_ARG, "bad sizes");
   if (nfrac == 0) return ED_OK;
   if (!npole || !E || !z || !peso || !Ei || !comp || !vm || !tau || !chi_iv || !chi_tau || (lreal && (!wr || !chi_w)))
@@ -3337,10 +3339,11 @@ int ed_chi_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const
   int64_t np = 0;
   for (int f = 0; f < nfrac; f++) {
     if (npole[f] < 0 || comp[f] < 0) return fail(ED_ERR_ARG, "bad fraction");
+    if (isign && !chi_sel_valid(isign[f])) return fail(ED_ERR_ARG, "isign must be 0 (both), +1 or -1");
     fr[f].p0 = (int32_t)np;
     fr[f].np = npole[f];
     fr[f].comp = comp[f];
-    fr[f].pad = 0;
+    fr[f].sel = isign ? isign[f] : kChiBoth;
     fr[f].peso = peso[f];
     fr[f].ei = Ei[f];
     np += npole[f];
@@ -3373,6 +3376,14 @@ int ed_chi_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const
   HIPCK(hipStreamSynchronize(st));
   HIPCK(le);
   return ED_OK;
+}
+
+int ed_chi_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const double* z, const double* peso,
+                     const double* Ei, const int32_t* comp, double beta, const double* vm, int32_t lmats,
+                     const double* tau, int32_t ltau, const double* wr, int32_t lreal, double eps, double* chi_iv,
+                     double* chi_tau, double* chi_w, void* stream) {
+  return ed_chi_add_poles_signed(nfrac, npole, E, z, peso, Ei, comp, nullptr, beta, vm, lmats, tau, ltau, wr, lreal,
+                                 eps, chi_iv, chi_tau, chi_w, stream);
 }
 
 int ed_sector_lanc_tridiag_dev(ed_sector* s, int32_t vtype, const void* v0_dev, int32_t nitermax,

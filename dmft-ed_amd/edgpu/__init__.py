@@ -10,7 +10,9 @@ Modules:
   farm        sector farm over ranks (torch.distributed / RCCL)
   gf          Green's functions (normal, nonSU2): device seeds, Lanczos, poles
   chi         spin and density susceptibilities of the kept states: diagonal
-              seeds (Sector.seed_diag), Lanczos, bosonic / tau / real-axis poles
+              seeds (Sector.seed_diag), Lanczos, bosonic / tau / real-axis poles;
+              pair and inter-orbital parts from two-operator seeds
+              (Sector.seed_pair)
   observables impurity observables and local energies of the kept states
               (observables_impurity / local_energy_impurity) from device
               vectors: Sector.nn_moments / Sector.expect

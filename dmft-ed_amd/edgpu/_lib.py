@@ -62,6 +62,7 @@ SIGNATURES = {
     "ed_sector_seed_batch": ([_P, _P, _i32, _i32, _P, _i32, _P, _i32, _P, _P, _P, _P], ctypes.c_int),
     "ed_sector_seed_plan": ([_P, _P, _i32, _P, _P, _i32, _P, _i32, _P, _P, _P, _P], ctypes.c_int),
     "ed_sector_seed_diag": ([_P, _i32, _P, _i32, _P, _i32, _P, _P, _P, _P], ctypes.c_int),
+    "ed_sector_seed_pair": ([_P, _P, _i32, _P, _i32, _P, _i32, _P, _P, _P, _P], ctypes.c_int),
     "ed_sector_twin_vector": ([_P, _P, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_nn_moments": ([_P, _i32, _P, _i32, _P, _P, _P], ctypes.c_int),
     "ed_sector_expect": ([_P, _i32, _P, _i32, _P, _P, _P, _P, _P], ctypes.c_int),
@@ -72,6 +73,8 @@ SIGNATURES = {
                         ctypes.c_int),
     "ed_chi_add_poles": ([_i32, _P, _P, _P, _P, _P, _P, _f64, _P, _i32, _P, _i32, _P, _i32, _f64, _P, _P, _P, _P],
                          ctypes.c_int),
+    "ed_chi_add_poles_signed": ([_i32, _P, _P, _P, _P, _P, _P, _P, _f64, _P, _i32, _P, _i32, _P, _i32, _f64, _P, _P,
+                                 _P, _P], ctypes.c_int),
     "ed_gpu_init": ([_P], ctypes.c_int),
     "ed_gpu_set_device": ([_i32], ctypes.c_int),
     "ed_gpu_build_sector": ([_i32, _i32, _i32, _P], ctypes.c_int),

@@ -27,6 +27,19 @@ Per kept state |n> (a twin entry's vector through `state_vector`):
 The off-diagonal density comes from the seeds n_a + n_b:
 chi[a,b] = chi[b,a] = (chi[n_a + n_b] - chi[n_a] - chi[n_b]) / 2 on all three
 grids, exact because the n_a commute and are real.
+
+With `pair` / `exc` the pair susceptibility of
+Delta_a = c_{a,up} c_{a,dw} (ED_GF_CHIPAIR.f90) and the inter-orbital density
+susceptibility of O_ab = sum_sigma c^+_{a,sigma} c_{b,sigma}
+(lanc_ed_build_densChi_mix_c, ED_GF_CHIDENS.f90:490-673) are built as well:
+chi_O(tau) = <O(tau) O^+(0)> of a non-Hermitian O is two one-sign fractions,
+the seed O^+|n> with isign = +1 and the seed O|n> with isign = -1 (the two
+branches above, one each).  Per kept state one ed_sector_seed_pair call
+(k_seed_pair) per target sector — every Delta_a|n> into (nup-1, ndw-1), every
+Delta_a^+|n> into (nup+1, ndw+1), every O_ab^+|n> into the state's own — writes
+straight into the stacked tensor of one batched Lanczos launch on that sector;
+O_ba = O_ab^+, so each inter-orbital tridiagonalisation is queued twice, with
++1 into [a,b] and with -1 into [b,a].
 """
 from __future__ import annotations
 
@@ -41,7 +54,7 @@ from ._lib import check
 from .diag import StateList, is_complex_vector, state_vector
 from .gf import SEED_BUFFER_BYTES, _device_vec, _dist, _peso_bz, _SectorCache, _tridiag_batch, realaxis, tridiag_poles
 from .params import EDConfig
-from .sectors import setup_pointers
+from .sectors import c_sector, cdg_sector, setup_pointers
 
 
 @dataclass
@@ -157,6 +170,14 @@ class Chi:
     dens_tot_iv: Optional[np.ndarray] = None
     dens_tot_tau: Optional[np.ndarray] = None
     dens_tot_w: Optional[np.ndarray] = None
+    # pair_*: (Norb,), chi of Delta_a = c_{a,up} c_{a,dw}; exc_*: (Norb, Norb), chi of
+    # O_ab = sum_sigma c^+_{a,sigma} c_{b,sigma}, zero on the diagonal
+    pair_iv: Optional[np.ndarray] = None
+    pair_tau: Optional[np.ndarray] = None
+    pair_w: Optional[np.ndarray] = None
+    exc_iv: Optional[np.ndarray] = None
+    exc_tau: Optional[np.ndarray] = None
+    exc_w: Optional[np.ndarray] = None
 
 
 def assemble(cfg: EDConfig, copt: ChiOptions, iv: np.ndarray, tau: np.ndarray, w: np.ndarray,
@@ -185,6 +206,82 @@ def assemble(cfg: EDConfig, copt: ChiOptions, iv: np.ndarray, tau: np.ndarray, w
     return out
 
 
+# ------------------------------------------------------------ pair and inter-orbital parts
+def n_components_ext(cfg: EDConfig, pair: bool = False, exc: bool = False) -> int:
+    """`n_components` plus, behind it, Norb pair components and the Norb x Norb
+    block of inter-orbital ones (its diagonal is never written)."""
+    return n_components(cfg) + (cfg.Norb if pair else 0) + (cfg.Norb * cfg.Norb if exc else 0)
+
+
+def pair_component(cfg: EDConfig, a: int) -> int:
+    return n_components(cfg) + a
+
+
+def exc_component(cfg: EDConfig, a: int, b: int, pair: bool = False) -> int:
+    return n_components(cfg) + (cfg.Norb if pair else 0) + a * cfg.Norb + b
+
+
+def exc_pairs(cfg: EDConfig) -> List[Tuple[int, int]]:
+    """Ordered pairs a != b: one seed O_ab^+|n> each."""
+    return [(a, b) for a in range(cfg.Norb) for b in range(cfg.Norb) if a != b]
+
+
+def pair_target(cfg: EDConfig, sec, isign: int):
+    """The sector of Delta_a|n> (isign -1: one up and one down electron fewer)
+    or Delta_a^+|n> (+1); None where it does not exist."""
+    step = cdg_sector if isign > 0 else c_sector
+    mid = step(cfg, sec, 1)
+    return None if mid is None else step(cfg, mid, 0)
+
+
+def seed_pair_calls(cfg: EDConfig, pair: bool = False, exc: bool = False):
+    """The ed_sector_seed_pair calls of one kept state in queue order: a list
+    of (target, images, terms, queue).  target: -1 / +1 the pair target sector
+    of that sign, 0 the kept state's own; images: rows (lev1, op1, lev2, op2),
+    (lev1, op1) acting first; terms: rows (p, q); queue[s]: the fractions of
+    seed s as (name, flat component, isign).
+
+      ("pair", a) -1   c_{a,up} c_{a,dw}|n>              ED_GF_CHIPAIR.f90:98-102
+      ("pair", a) +1   c^+_{a,dw} c^+_{a,up}|n>          ED_GF_CHIPAIR.f90:144-148
+      ("exc", a, b) +1 and ("exc", b, a) -1, one seed
+                       sum_sigma c^+_{b,sigma} c_{a,sigma}|n>
+                                                          ED_GF_CHIDENS.f90:523-586, :596-659
+    """
+    No, Ns = cfg.Norb, cfg.Ns
+    out = []
+    if pair:
+        one = [(a, -1) for a in range(No)]
+        out.append((-1, [(a + Ns, 0, a, 0) for a in range(No)], one,
+                    [[(("pair", a), pair_component(cfg, a), -1)] for a in range(No)]))
+        out.append((+1, [(a, 1, a + Ns, 1) for a in range(No)], one,
+                    [[(("pair", a), pair_component(cfg, a), +1)] for a in range(No)]))
+    if exc and No > 1:
+        images, terms, queue = [], [], []
+        for a, b in exc_pairs(cfg):
+            terms.append((len(images), len(images) + 1))
+            images += [(a, 0, b, 1), (a + Ns, 0, b + Ns, 1)]
+            queue.append([(("exc", a, b), exc_component(cfg, a, b, pair), +1),
+                          (("exc", b, a), exc_component(cfg, b, a, pair), -1)])
+        out.append((0, images, terms, queue))
+    return out
+
+
+def assemble_ext(cfg: EDConfig, copt: ChiOptions, iv: np.ndarray, tau: np.ndarray, w: np.ndarray,
+                 spin: bool = True, dens: bool = True, pair: bool = False, exc: bool = False) -> Chi:
+    """`assemble` of the leading components, then the pair rows and the
+    inter-orbital block of the components behind them."""
+    No = cfg.Norb
+    out = assemble(cfg, copt, iv, tau, w, spin=spin, dens=dens)
+    if pair:
+        p0 = pair_component(cfg, 0)
+        out.pair_iv, out.pair_tau, out.pair_w = (np.array(x[p0:p0 + No]) for x in (iv, tau, w))
+    if exc:
+        e0 = exc_component(cfg, 0, 0, pair)
+        out.exc_iv, out.exc_tau, out.exc_w = (np.array(x[e0:e0 + No * No]).reshape((No, No) + x.shape[1:])
+                                              for x in (iv, tau, w))
+    return out
+
+
 # ------------------------------------------------------------ the pole sums
 class ChiPoleSums:
     """Device side of add_to_lanczos_spinChi (ED_GF_CHISPIN.f90:254-323), the
@@ -192,8 +289,9 @@ class ChiPoleSums:
     iv (ncomp, Lmats+1) complex, tau (ncomp, Ltau+1) real and w (ncomp, Lreal)
     complex live in HBM, `add` queues one tridiagonalisation's poles for a
     flat component and `flush` sums every queued fraction in one launch of
-    ed_chi_add_poles, in queue order (within a fraction every pole with
-    isign = +1, then every pole with -1)."""
+    ed_chi_add_poles_signed, in queue order (within a fraction every pole with
+    isign = +1, then every pole with -1; a fraction added with isign = +-1
+    takes that branch alone)."""
 
     def __init__(self, ncomp: int, vm: np.ndarray, tau: np.ndarray, wr: np.ndarray, beta: float, eps: float,
                  device: int):
@@ -210,9 +308,10 @@ class ChiPoleSums:
         self.w = torch.zeros((ncomp, len(wr)), dtype=torch.complex128, device=self.dev)
         self._q = []
 
-    def add(self, comp: int, peso: float, Ei: float, E: np.ndarray, z: np.ndarray) -> None:
-        assert 0 <= int(comp) < self.ncomp
-        self._q.append((int(comp), float(peso), float(Ei), np.asarray(E, np.float64), np.asarray(z, np.float64)))
+    def add(self, comp: int, peso: float, Ei: float, E: np.ndarray, z: np.ndarray, isign: int = 0) -> None:
+        assert 0 <= int(comp) < self.ncomp and int(isign) in (0, 1, -1)
+        self._q.append((int(comp), float(peso), float(Ei), np.asarray(E, np.float64), np.asarray(z, np.float64),
+                        int(isign)))
 
     def flush(self) -> None:
         import torch
@@ -226,21 +325,26 @@ class ChiPoleSums:
         peso = np.array([t[1] for t in q], dtype=np.float64)
         ei = np.array([t[2] for t in q], dtype=np.float64)
         comp = np.array([t[0] for t in q], dtype=np.int32)
+        isign = np.array([t[5] for t in q], dtype=np.int32)
         st = torch.cuda.current_stream(self.dev)
         P = ctypes.c_void_p
-        check(_lib.load().ed_chi_add_poles(len(q), P(npole.ctypes.data), P(E.ctypes.data), P(z.ctypes.data),
-                                           P(peso.ctypes.data), P(ei.ctypes.data), P(comp.ctypes.data), self.beta,
-                                           P(self.vm.data_ptr()), self.vm.numel() - 1, P(self.tg.data_ptr()),
-                                           self.tg.numel() - 1, P(self.wr.data_ptr()), self.wr.numel(), self.eps,
-                                           P(self.iv.data_ptr()), P(self.tau.data_ptr()), P(self.w.data_ptr()),
-                                           P(st.cuda_stream)), "ed_chi_add_poles")
+        check(_lib.load().ed_chi_add_poles_signed(
+            len(q), P(npole.ctypes.data), P(E.ctypes.data), P(z.ctypes.data), P(peso.ctypes.data), P(ei.ctypes.data),
+            P(comp.ctypes.data), P(isign.ctypes.data), self.beta, P(self.vm.data_ptr()), self.vm.numel() - 1,
+            P(self.tg.data_ptr()), self.tg.numel() - 1, P(self.wr.data_ptr()), self.wr.numel(), self.eps,
+            P(self.iv.data_ptr()), P(self.tau.data_ptr()), P(self.w.data_ptr()), P(st.cuda_stream)),
+            "ed_chi_add_poles_signed")
 
     def to_host(self):
         return self.iv.cpu().numpy(), self.tau.cpu().numpy(), self.w.cpu().numpy()
 
 
 # ------------------------------------------------------------ the build
-def _check(cfg: EDConfig, states: StateList, copt: ChiOptions) -> None:
+def _check(cfg: EDConfig, states: StateList, copt: ChiOptions, pair: bool = False, exc: bool = False) -> None:
+    if (pair or exc) and cfg.ed_mode == "nonsu2" and cfg.Jz_basis:
+        raise NotImplementedError("build_chi: " + " and ".join(n for n, on in (("pair", pair), ("exc", exc)) if on)
+                                  + " in the Jz_basis is not built: the seeds of one call reach different "
+                                  "(n, twoJz) sectors")
     if cfg.ed_mode == "superc":
         raise NotImplementedError("build_chi: ed_mode='superc' is not built: a superc twin vector needs "
                                   "superc_twin_sign and no susceptibility test covers it")
@@ -254,27 +358,32 @@ def _check(cfg: EDConfig, states: StateList, copt: ChiOptions) -> None:
 
 
 def build_chi(cfg: EDConfig, states: StateList, copt: Optional[ChiOptions] = None, device: int = 0,
-              spin: bool = True, dens: bool = True, record: Optional[list] = None) -> Chi:
+              spin: bool = True, dens: bool = True, record: Optional[list] = None, pair: bool = False,
+              exc: bool = False) -> Chi:
     """spinChi and densChi of buildChi_impurity (ED_GREENS_FUNCTIONS.f90:72-106)
-    on the three grids, as a `Chi`; see the module docstring.  `record` gets
-    one dict per fraction (name, component, kept state, isector, norm2, alfa,
-    beta, nlanc) in queue order.  Refused: ed_mode superc, and a
-    torch.distributed world larger than 1."""
+    on the three grids and, with `pair` / `exc`, its pair and inter-orbital
+    density parts, as a `Chi`; see the module docstring.  `record` gets one
+    dict per fraction (name, component, kept state, isector, norm2, alfa,
+    beta, nlanc, isign) in queue order: per kept state the spin and density
+    seeds, the pair -1 seeds by orbital, the pair +1 seeds, the inter-orbital
+    seeds (each queued with +1 and then -1).  Refused: ed_mode superc, a
+    torch.distributed world larger than 1, and pair / exc in the Jz_basis."""
     import torch
 
     copt = copt or ChiOptions()
-    _check(cfg, states, copt)
+    _check(cfg, states, copt, pair, exc)
     table = seed_table(cfg, spin, dens)
+    calls = seed_pair_calls(cfg, pair, exc)
     vm, tg = bosonic_matsubara(copt.beta, copt.Lmats), tau_grid(copt.beta, copt.ltau)
     wr = realaxis(copt.wini, copt.wfin, copt.Lreal)
-    poles = ChiPoleSums(n_components(cfg), vm, tg, wr, copt.beta, copt.eps, device)
+    poles = ChiPoleSums(n_components_ext(cfg, pair, exc), vm, tg, wr, copt.beta, copt.eps, device)
     zeta = states.zeta if states.finite_t else float(states.size)
     levels = seed_levels(cfg)
     secs = setup_pointers(cfg)
     torch.cuda.set_device(device)
     cache = _SectorCache(cfg, copt, device)
     try:
-        for k, isec in enumerate(states.sectors if table else []):
+        for k, isec in enumerate(states.sectors if table or calls else []):
             sec = secs[isec - 1]
             vec = state_vector(cfg, states, k, device, lambda s: cache.get(s, False))
             if vec is None:
@@ -301,9 +410,32 @@ def build_chi(cfg: EDConfig, states: StateList, copt: Optional[ChiOptions] = Non
                     E, z = tridiag_poles(a[row], b[row], nlanc, first_row=True)
                     if record is not None:
                         record.append(dict(name=name, comp=comp, state=k, isector=isec, norm2=float(n2[q]),
-                                           alfa=a[row], beta=b[row], nlanc=int(nl[row])))
+                                           alfa=a[row], beta=b[row], nlanc=int(nl[row]), isign=0))
                     poles.add(comp, _peso_bz(states, k, 1.0, float(n2[q]), zeta), states.energies[k], E, z)
+            for target, images, terms, queue in calls:
+                tsec = sec if target == 0 else pair_target(cfg, sec, target)
+                if tsec is None:                                          # no such sector: no seed
+                    continue
+                St = cache.get(tsec, True)
+                nlanc = min(St.dim, copt.lanc_nGFiter)
+                step = max(1, min(len(terms), SEED_BUFFER_BYTES // (St.dim * (16 if cplx else 8))))
+                for q0 in range(0, len(terms), step):
+                    buf, n2 = S.seed_pair(x, St, images, terms[q0:q0 + step])
+                    keep = [q for q, v in enumerate(n2) if v != 0.0]
+                    if not keep:
+                        continue
+                    stacked = buf if len(keep) == len(n2) else buf[torch.tensor(keep, device=buf.device)]
+                    torch.cuda.current_stream(stacked.device).synchronize()
+                    a, b, nl = _tridiag_batch(St, stacked, nlanc, not cplx, copt.threshold)
+                    for row, q in enumerate(keep):
+                        E, z = tridiag_poles(a[row], b[row], nlanc, first_row=True)
+                        for name, comp, isign in queue[q0 + q]:
+                            if record is not None:
+                                record.append(dict(name=name, comp=comp, state=k, isector=isec, norm2=float(n2[q]),
+                                                   alfa=a[row], beta=b[row], nlanc=int(nl[row]), isign=isign))
+                            poles.add(comp, _peso_bz(states, k, 1.0, float(n2[q]), zeta), states.energies[k], E, z,
+                                      isign)
     finally:
         cache.close()
     poles.flush()
-    return assemble(cfg, copt, *poles.to_host(), spin=spin, dens=dens)
+    return assemble_ext(cfg, copt, *poles.to_host(), spin=spin, dens=dens, pair=pair, exc=exc)

@@ -341,6 +341,32 @@ class Sector:
                                               _tptr(out), _ptr(n2), _stream_ptr(st)), "ed_sector_seed_diag")
         return out, n2
 
+    def seed_pair(self, vec, dst: "Sector", images, terms, out=None):
+        """Seeds whose images are products of two ladder operators
+        (ed_sector_seed_pair): `vec` lives in this sector, `dst` is the sector
+        every image maps it into (this one is allowed).  images: rows
+        (lev1, op1, lev2, op2), op 0 = c and 1 = c^+ on the 0-based bit, op1
+        on lev1 acting first; terms: rows (p, q) of image indices, q < 0 for
+        image p alone.  The vvinit loops of the pair susceptibility
+        (ED_GF_CHIPAIR.f90:98-102, :144-148) and of the inter-orbital density
+        susceptibility (ED_GF_CHIDENS.f90:523-586, :596-659).  Returns (device
+        tensor (nseed, dst.dim) of the vector's type, norm2 (nseed,)); a seed
+        with norm2 == 0 is all zero.  out: a contiguous device tensor of that
+        shape and type to write into."""
+        im = np.ascontiguousarray(images, dtype=np.int32).reshape(-1, 4)
+        tm = np.ascontiguousarray(terms, dtype=np.int32).reshape(-1, 2)
+        vt, x, st = self._state_arg(vec)
+        if dst.device != self.device:
+            raise ValueError("seed_pair: sectors on different devices")
+        if out is None:
+            out = self._out_array((tm.shape[0], dst.dim), vt, True)
+        elif tuple(out.shape) != (tm.shape[0], dst.dim) or out.dtype != x.dtype or not out.is_contiguous():
+            raise ValueError("seed_pair: out must be a contiguous (nseed, dst.dim) tensor of the vector's type")
+        n2 = np.zeros(tm.shape[0])
+        check(_lib.load().ed_sector_seed_pair(self._h, dst.handle, im.shape[0], _ptr(im), tm.shape[0], _ptr(tm), vt,
+                                              _tptr(x), _tptr(out), _ptr(n2), _stream_ptr(st)), "ed_sector_seed_pair")
+        return out, n2
+
     # ---------------------------------------------------------- twin sectors
     def twin_vector(self, dst: "Sector", vec):
         """The vector of a twin entry of the state list (es_return_cvector,

@@ -43,6 +43,10 @@
  *                                ED_GF_NORMAL.f90:159-174, ED_GF_NORMAL.f90:312-344
  *   ed_sector_seed_plan       <- the six vvinit loops of lanc_build_gf_superc_c
  *                                ED_GF_SUPERC.f90:119-439
+ *   ed_sector_seed_pair       <- the vvinit loops of the pair susceptibility
+ *                                ED_GF_CHIPAIR.f90:98-102, ED_GF_CHIPAIR.f90:144-148 and of
+ *                                lanc_ed_build_densChi_mix_c ED_GF_CHIDENS.f90:523-586,
+ *                                ED_GF_CHIDENS.f90:596-659
  */
 #ifndef ED_GPU_H
 #define ED_GPU_H
@@ -405,6 +409,29 @@ int ed_sector_seed_diag(const ed_sector* s, int32_t nlev, const int32_t* levels,
                         int32_t nseed, const double* weight,
                         int32_t vtype, const void* src_vec,
                         void* seeds, double* norm2, void* stream);
+/* Seeds whose images are products of two ladder operators, every one of a
+ * kept state and target sector in one pass: the vvinit loops of the pair
+ * susceptibility, ED_GF_CHIPAIR.f90:98-102 (c_{a,dw} then c_{a,up}) and
+ * ED_GF_CHIPAIR.f90:144-148 (c^+_{a,up} then c^+_{a,dw}), and of
+ * lanc_ed_build_densChi_mix_c, ED_GF_CHIDENS.f90:523-586 (c^+_b c_a) and
+ * ED_GF_CHIDENS.f90:596-659 (c^+_a c_b), with their dot_product and divide.
+ * Image l is images[l] = (lev1, op1, lev2, op2): op2 (0: c, 1: c^+) on the
+ * 0-based bit lev2 applied after op1 on lev1 to |src_vec>, lev1 != lev2; seed
+ * s is image terms[2s], or image terms[2s] + image terms[2s+1] (a negative
+ * second index: the first alone), with unit coefficients, normalised; that is
+ * the arithmetic of ed_sector_apply_op into the intermediate sector followed
+ * by ed_sector_apply_op_acc(coef = 1).  src == dst is allowed.  ED_ERR_ARG,
+ * before anything is launched, unless 1 <= nimg <= 12, 1 <= nseed <= 12,
+ * lev1 != lev2, every image maps src into dst exactly, no two images are the
+ * same, every index is below nimg and the two of a seed differ, the sectors
+ * are on one device and of one model, vtype is 0 or 1 and seeds does not
+ * overlap src_vec.  seeds ([nseed][dst->dim]), norm2, determinism, row-split
+ * sectors and synchronisation as ed_sector_seed_batch. */
+int ed_sector_seed_pair(const ed_sector* src, const ed_sector* dst,
+                        int32_t nimg, const int32_t* images,
+                        int32_t nseed, const int32_t* terms,
+                        int32_t vtype, const void* src_vec,
+                        void* seeds, double* norm2, void* stream);
 /* Vector of a twin entry of the state list (es_return_cvector,
  * ED_EIGENSPACE.f90:414-445; twin_sector_order and flip_state,
  * ED_SETUP.f90:1123-1186), from its partner's vector:
@@ -501,6 +528,17 @@ int ed_chi_add_poles(int32_t nfrac, const int32_t* npole, const double* E, const
                      const double* Ei, const int32_t* comp, double beta, const double* vm, int32_t lmats,
                      const double* tau, int32_t ltau, const double* wr, int32_t lreal, double eps, double* chi_iv,
                      double* chi_tau, double* chi_w, void* stream);
+/* The same with one isign call per fraction where asked: isign[f] = 0 is the
+ * fraction of ed_chi_add_poles (+1 and then -1, the same additions in the same
+ * order), +1 adds only the -D terms with the exp(-tau D) one and one s_j at
+ * chi_iv[comp][0] (a seed O^+|n> of a non-Hermitian O), -1 only the +D terms
+ * with exp(-(beta - tau) D) and one s_j (a seed O|n>).  isign == NULL: every
+ * fraction takes both.  Any other value: ED_ERR_ARG, nothing is launched. */
+int ed_chi_add_poles_signed(int32_t nfrac, const int32_t* npole, const double* E, const double* z,
+                            const double* peso, const double* Ei, const int32_t* comp, const int32_t* isign,
+                            double beta, const double* vm, int32_t lmats, const double* tau, int32_t ltau,
+                            const double* wr, int32_t lreal, double eps, double* chi_iv, double* chi_tau,
+                            double* chi_w, void* stream);
 
 /* ------------------------------------------------------ reference-style API */
 int ed_gpu_init(const ed_params* p);          /* ed_init_solver parameter hand-over */
