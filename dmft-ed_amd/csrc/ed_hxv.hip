@@ -492,18 +492,86 @@ int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t o
   return ED_OK;
 }
 
-// ------------------------------------------------ fused GF seeds (ed_seed.hpp)
+// ------------------------------------------------ fused seeds (ed_seed.hpp, ed_chi.hpp)
+// The seed pipeline, one for the four entries below: the entry validates its
+// own table or plan, seed_check_io checks what they share, and seed_run
+// launches the entry's gather kernel, k_seed_scale and the download of the
+// norms.  Every check comes before the first launch: a refused call leaves
+// `seeds` untouched.
+static constexpr int kSeedMaxGrid = 1024;  // partials per seed: the cap kObsMaxGrid puts on the observables' grids
+
+// The kernel arguments keep their sizes: the kernels are compiled for these.
+static_assert(sizeof(SeedPlan) == 84 && sizeof(PairPlan) == 80 && sizeof(SeedTable) == 3136 &&
+                  sizeof(DiagTable) == 1568,
+              "a seed kernel's argument changed size");
+
+static bool same_model(const EdModel& a, const EdModel& b) {
+  return a.ns == b.ns && a.norb == b.norb && a.nbath == b.nbath && a.nspin == b.nspin && a.mode == b.mode &&
+         a.bath == b.bath && a.jz == b.jz;
+}
+
+// src_vec: [src->dim] read by the gather; seeds: [nseed][dst->dim] written by
+// it.  The gather kernels read x[idx_src(s)] while other threads store whole
+// output rows, so the two may not overlap.  src == dst is allowed.
+static int seed_check_io(const ed_sector* src, const ed_sector* dst, int32_t nseed, int32_t vtype,
+                         const void* src_vec, const void* seeds) {
+  if (!src || !dst || !src_vec || !seeds) return fail(ED_ERR_ARG, "null");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (src->device != dst->device) return fail(ED_ERR_ARG, "sectors on different devices");
+  if (!same_model(src->Mh, dst->Mh)) return fail(ED_ERR_ARG, "sectors of different models");
+  CK(whole_only(src));
+  CK(whole_only(dst));
+  const size_t vs = vtype ? 16 : 8;
+  const uintptr_t a = (uintptr_t)src_vec, b = (uintptr_t)seeds;
+  if (a < b + (size_t)nseed * dst->dim * vs && b < a + (size_t)src->dim * vs)
+    return fail(ED_ERR_ARG, "seeds overlaps src_vec");
+  return ED_OK;
+}
+
+// launch_gather(vc_tag, g, partials, st) issues the entry's gather kernel with
+// grid g on st: it leaves the unnormalised seeds [nseed][dst->dim] and one
+// partial of sum |seed_q|^2 per seed and block.  vc_tag is
+// std::bool_constant<VC>, VC the kernel's vector type.
+extern "C++" template <class Launch>
+static int seed_run(const ed_sector* dst, int32_t nseed, int32_t vtype, void* seeds, double* norm2, void* stream,
+                    Launch launch_gather) {
+  HIPCK(hipSetDevice(dst->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t dim = dst->dim;
+  const int g = std::min(grid_for(dim), kSeedMaxGrid);
+  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
+  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
+  DevFree fr{part, st};
+  PinnedLease pin((size_t)nseed * sizeof(double), st);
+  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
+  double* dn = part + (size_t)nseed * g;
+  double* hn = (double*)pin.p;
+  if (vtype) {
+    launch_gather(std::true_type{}, g, part, st);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
+  } else {
+    launch_gather(std::false_type{}, g, part, st);
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
+  }
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
+  return ED_OK;
+}
+
 // Every seed of one (source vector, operator type, target sector) group: the
 // vvinit loops ED_GF_NORMAL.f90:159-174 and :312-344 with their dot_product
 // and divide, as one gather pass over dst's rows and one scale pass.
-static constexpr int kSeedMaxGrid = 1024;  // partials per seed: the cap kObsMaxGrid puts on the observables' grids
 int ed_sector_seed_batch(const ed_sector* src, const ed_sector* dst, int32_t op, int32_t nlev,
                          const int32_t* levels, int32_t nseed, const double* coef, int32_t vtype,
                          const void* src_vec, void* seeds, double* norm2, void* stream) {
-  if (!src || !dst || !levels || !coef || !src_vec || !seeds || !norm2) return fail(ED_ERR_ARG, "null");
-  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (!levels || !coef || !norm2) return fail(ED_ERR_ARG, "null");
   if (nlev < 1 || nlev > kSeedMaxLev) return fail(ED_ERR_ARG, "nlev must be 1..2*ED_MAX_NORB");
   if (nseed < 1 || nseed > kSeedMaxSeeds) return fail(ED_ERR_ARG, "nseed must be 1..32");
+  CK(seed_check_io(src, dst, nseed, vtype, src_vec, seeds));
   SeedTable T{};
   T.nlev = nlev;
   T.nseed = nseed;
@@ -521,136 +589,57 @@ int ed_sector_seed_batch(const ed_sector* src, const ed_sector* dst, int32_t op,
       if (!vtype && T.ci[q][l] != 0.0) return fail(ED_ERR_ARG, "complex coefficient needs vtype=1");
       if (T.cr[q][l] != 0.0 || T.ci[q][l] != 0.0) T.used[q] |= (uint8_t)(1u << l);
     }
-  CK(whole_only(src));
-  CK(whole_only(dst));
-  HIPCK(hipSetDevice(src->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t dim = dst->dim;
-  const int g = std::min(grid_for(dim), kSeedMaxGrid);
-  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
-  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
-  DevFree fr{part, st};
-  PinnedLease pin((size_t)nseed * sizeof(double), st);
-  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
-  double* dn = part + (size_t)nseed * g;
-  double* hn = (double*)pin.p;
   const DevIndex idx{src->d_off, src->d_rank, src->T.ns, src->T.nst - 1};
-  if (vtype) {
-    hipLaunchKernelGGL(k_seed_gather<true>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, op, T,
-                       (const double2*)src_vec, (double2*)seeds, part);
-    HIPCK(hipGetLastError());
-    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
-  } else {
-    hipLaunchKernelGGL(k_seed_gather<false>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, op, T,
-                       (const double*)src_vec, (double*)seeds, part);
-    HIPCK(hipGetLastError());
-    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
-  }
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
-  return ED_OK;
+  return seed_run(dst, nseed, vtype, seeds, norm2, stream, [&](auto vc, int g, double* part, hipStream_t st) {
+    constexpr bool VC = decltype(vc)::value;
+    hipLaunchKernelGGL(k_seed_gather<VC>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dst->dim, idx, op, T,
+                       (const val_t<VC>*)src_vec, (val_t<VC>*)seeds, part);
+  });
 }
 
 // Seeds whose images mix operator types: the six vvinit loops of
 // lanc_build_gf_superc_c (ED_GF_SUPERC.f90:119-439) per kept state, three per
-// target sector, with their dot_product and divide.  Every check comes before
-// the first launch: a refused call leaves `seeds` untouched.
+// target sector, with their dot_product and divide.  seed_plan_compile checks
+// that every image maps src into dst.
 int ed_sector_seed_plan(const ed_sector* src, const ed_sector* dst, int32_t nlev, const int32_t* levels,
                         const int32_t* ops, int32_t nseed, const int32_t* terms, int32_t vtype,
                         const void* src_vec, void* seeds, double* norm2, void* stream) {
-  if (!src || !dst || !levels || !ops || !terms || !src_vec || !seeds || !norm2) return fail(ED_ERR_ARG, "null");
-  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (!levels || !ops || !terms || !norm2) return fail(ED_ERR_ARG, "null");
   if (nlev < 1 || nlev > kSeedMaxLev) return fail(ED_ERR_ARG, "nlev must be 1..2*ED_MAX_NORB");
   if (nseed < 1 || nseed > kSeedMaxSeeds) return fail(ED_ERR_ARG, "nseed must be 1..32");
-  // the kernel's index tables do not bounds-check: every image must map src into dst
-  for (int l = 0; l < nlev; l++) CK(check_op_target(src, dst, ops[l], levels[l]));
+  CK(seed_check_io(src, dst, nseed, vtype, src_vec, seeds));
   SeedPlan P;
   if (seed_plan_compile(seed_sectors(src, dst), nlev, levels, ops, nseed, terms, &P) != ED_OK)
-    return fail(ED_ERR_ARG, "seed plan: (level, op) pairs must be distinct, p and q below nlev, p != q");
-  CK(whole_only(src));
-  CK(whole_only(dst));
-  HIPCK(hipSetDevice(src->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t dim = dst->dim;
-  const int g = std::min(grid_for(dim), kSeedMaxGrid);
-  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
-  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
-  DevFree fr{part, st};
-  PinnedLease pin((size_t)nseed * sizeof(double), st);
-  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
-  double* dn = part + (size_t)nseed * g;
-  double* hn = (double*)pin.p;
+    return fail(ED_ERR_ARG, "seed plan: every image maps src into dst, (level, op) pairs must be distinct, "
+                            "p and q below nlev, p != q");
   const DevIndex idx{src->d_off, src->d_rank, src->T.ns, src->T.nst - 1};
-  if (vtype) {
-    hipLaunchKernelGGL(k_seed_plan<true>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
-                       (const double2*)src_vec, (double2*)seeds, part);
-    HIPCK(hipGetLastError());
-    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
-  } else {
-    hipLaunchKernelGGL(k_seed_plan<false>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
-                       (const double*)src_vec, (double*)seeds, part);
-    HIPCK(hipGetLastError());
-    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
-  }
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
-  return ED_OK;
+  return seed_run(dst, nseed, vtype, seeds, norm2, stream, [&](auto vc, int g, double* part, hipStream_t st) {
+    constexpr bool VC = decltype(vc)::value;
+    hipLaunchKernelGGL(k_seed_plan<VC>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dst->dim, idx, P,
+                       (const val_t<VC>*)src_vec, (val_t<VC>*)seeds, part);
+  });
 }
 
 // Seeds of operators diagonal in the Fock basis (ed_chi.hpp): the vvinit loops
 // of lanc_ed_build_spinChi_c (ED_GF_CHISPIN.f90:98-103), _tot_c
 // (ED_GF_CHISPIN.f90:194-199) and of the density builders
 // (ED_GF_CHIDENS.f90:127-132) for every operator of one kept state, with their
-// dot_product and divide.  The seed stays in s; every check comes before the
-// first launch: a refused call leaves `seeds` untouched.
+// dot_product and divide.  The seed stays in s.
 int ed_sector_seed_diag(const ed_sector* s, int32_t nlev, const int32_t* levels, int32_t nseed,
                         const double* weight, int32_t vtype, const void* src_vec, void* seeds, double* norm2,
                         void* stream) {
-  if (!s || !levels || !weight || !src_vec || !seeds || !norm2) return fail(ED_ERR_ARG, "null");
-  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (!levels || !weight || !norm2) return fail(ED_ERR_ARG, "null");
   if (nlev < 1 || nlev > kDiagMaxLev) return fail(ED_ERR_ARG, "nlev must be 1..2*ED_MAX_NORB");
   if (nseed < 1 || nseed > kDiagMaxSeeds) return fail(ED_ERR_ARG, "nseed must be 1..32");
+  CK(seed_check_io(s, s, nseed, vtype, src_vec, seeds));
   DiagTable T;
   if (seed_diag_compile(s->Mh.ns, nlev, levels, nseed, weight, &T) != ED_OK)
     return fail(ED_ERR_ARG, "seed table: levels must be distinct and below 2*Ns");
-  const size_t vs = vtype ? 16 : 8;
-  {
-    const uintptr_t a = (uintptr_t)src_vec, b = (uintptr_t)seeds;
-    if (a < b + (size_t)nseed * s->dim * vs && b < a + (size_t)s->dim * vs)
-      return fail(ED_ERR_ARG, "seeds overlaps src_vec");
-  }
-  CK(whole_only(s));
-  HIPCK(hipSetDevice(s->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t dim = s->dim;
-  const int g = std::min(grid_for(dim), kSeedMaxGrid);
-  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
-  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
-  DevFree fr{part, st};
-  PinnedLease pin((size_t)nseed * sizeof(double), st);
-  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
-  double* dn = part + (size_t)nseed * g;
-  double* hn = (double*)pin.p;
-  if (vtype) {
-    hipLaunchKernelGGL(k_seed_diag<true>, dim3(g), dim3(kBlock), 0, st, s->d_map, dim, T, (const double2*)src_vec,
-                       (double2*)seeds, part);
-    HIPCK(hipGetLastError());
-    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
-  } else {
-    hipLaunchKernelGGL(k_seed_diag<false>, dim3(g), dim3(kBlock), 0, st, s->d_map, dim, T, (const double*)src_vec,
-                       (double*)seeds, part);
-    HIPCK(hipGetLastError());
-    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
-  }
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
-  return ED_OK;
+  return seed_run(s, nseed, vtype, seeds, norm2, stream, [&](auto vc, int g, double* part, hipStream_t st) {
+    constexpr bool VC = decltype(vc)::value;
+    hipLaunchKernelGGL(k_seed_diag<VC>, dim3(g), dim3(kBlock), 0, st, s->d_map, s->dim, T,
+                       (const val_t<VC>*)src_vec, (val_t<VC>*)seeds, part);
+  });
 }
 
 // Seeds whose images are products of two ladder operators (ed_chi.hpp,
@@ -658,63 +647,25 @@ int ed_sector_seed_diag(const ed_sector* s, int32_t nlev, const int32_t* levels,
 // (ED_GF_CHIPAIR.f90:98-102, :144-148) and of lanc_ed_build_densChi_mix_c
 // (ED_GF_CHIDENS.f90:523-586, :596-659) for every operator of one kept state,
 // with their dot_product and divide.  src == dst is allowed (the inter-orbital
-// seeds stay in the kept state's sector).  Every check comes before the first
-// launch: a refused call leaves `seeds` untouched.
+// seeds stay in the kept state's sector).  seed_pair_compile checks that every
+// image maps src into dst.
 int ed_sector_seed_pair(const ed_sector* src, const ed_sector* dst, int32_t nimg, const int32_t* images,
                         int32_t nseed, const int32_t* terms, int32_t vtype, const void* src_vec, void* seeds,
                         double* norm2, void* stream) {
-  if (!src || !dst || !images || !terms || !src_vec || !seeds || !norm2) return fail(ED_ERR_ARG, "null");
-  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (!images || !terms || !norm2) return fail(ED_ERR_ARG, "null");
   if (nimg < 1 || nimg > kPairMaxImg) return fail(ED_ERR_ARG, "nimg must be 1..12");
   if (nseed < 1 || nseed > kPairMaxSeeds) return fail(ED_ERR_ARG, "nseed must be 1..12");
-  if (src->device != dst->device) return fail(ED_ERR_ARG, "sectors on different devices");
-  {
-    const EdModel &a = src->Mh, &b = dst->Mh;
-    if (a.ns != b.ns || a.norb != b.norb || a.nbath != b.nbath || a.nspin != b.nspin || a.mode != b.mode ||
-        a.bath != b.bath || a.jz != b.jz)
-      return fail(ED_ERR_ARG, "sectors of different models");
-  }
-  // the kernel's index tables do not bounds-check: every image must map src into dst
+  CK(seed_check_io(src, dst, nseed, vtype, src_vec, seeds));
   PairPlan P;
   if (seed_pair_compile(seed_sectors(src, dst), nimg, images, nseed, terms, &P) != ED_OK)
     return fail(ED_ERR_ARG, "seed pair plan: lev1 != lev2, every image maps src into dst, images distinct, "
                             "p and q below nimg, p != q");
-  const size_t vs = vtype ? 16 : 8;
-  {
-    const uintptr_t a = (uintptr_t)src_vec, b = (uintptr_t)seeds;
-    if (a < b + (size_t)nseed * dst->dim * vs && b < a + (size_t)src->dim * vs)
-      return fail(ED_ERR_ARG, "seeds overlaps src_vec");
-  }
-  CK(whole_only(src));
-  CK(whole_only(dst));
-  HIPCK(hipSetDevice(src->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t dim = dst->dim;
-  const int g = std::min(grid_for(dim), kSeedMaxGrid);
-  double* part = nullptr;  // partials [nseed][g] | norm2 [nseed]
-  HIPCK(hipMallocAsync((void**)&part, ((size_t)nseed * g + nseed) * sizeof(double), st));
-  DevFree fr{part, st};
-  PinnedLease pin((size_t)nseed * sizeof(double), st);
-  if (!pin.p) return fail(ED_ERR_OOM, "pinned staging");
-  double* dn = part + (size_t)nseed * g;
-  double* hn = (double*)pin.p;
   const DevIndex idx{src->d_off, src->d_rank, src->T.ns, src->T.nst - 1};
-  if (vtype) {
-    hipLaunchKernelGGL(k_seed_pair<true>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
-                       (const double2*)src_vec, (double2*)seeds, part);
-    HIPCK(hipGetLastError());
-    hipLaunchKernelGGL(k_seed_scale<true>, dim3(g, nseed), dim3(kBlock), 0, st, (double2*)seeds, dim, part, g, dn);
-  } else {
-    hipLaunchKernelGGL(k_seed_pair<false>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dim, idx, P,
-                       (const double*)src_vec, (double*)seeds, part);
-    HIPCK(hipGetLastError());
-    hipLaunchKernelGGL(k_seed_scale<false>, dim3(g, nseed), dim3(kBlock), 0, st, (double*)seeds, dim, part, g, dn);
-  }
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(hn, dn, (size_t)nseed * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCK(hipStreamSynchronize(st));
-  memcpy(norm2, hn, (size_t)nseed * sizeof(double));
-  return ED_OK;
+  return seed_run(dst, nseed, vtype, seeds, norm2, stream, [&](auto vc, int g, double* part, hipStream_t st) {
+    constexpr bool VC = decltype(vc)::value;
+    hipLaunchKernelGGL(k_seed_pair<VC>, dim3(g), dim3(kBlock), 0, st, dst->d_map, dst->dim, idx, P,
+                       (const val_t<VC>*)src_vec, (val_t<VC>*)seeds, part);
+  });
 }
 
 // ------------------------------------------------ twin-sector vectors
@@ -723,10 +674,8 @@ int ed_sector_seed_pair(const ed_sector* src, const ed_sector* dst, int32_t nimg
 static int check_twin_pair(const ed_sector* src, const ed_sector* dst) {
   if (!src || !dst) return fail(ED_ERR_ARG, "null");
   if (src->device != dst->device) return fail(ED_ERR_ARG, "sectors on different devices");
-  const EdModel &a = src->Mh, &b = dst->Mh;
-  if (a.ns != b.ns || a.norb != b.norb || a.nbath != b.nbath || a.nspin != b.nspin || a.mode != b.mode ||
-      a.bath != b.bath || a.jz != b.jz)
-    return fail(ED_ERR_ARG, "sectors of different models");
+  const EdModel& a = src->Mh;
+  if (!same_model(a, dst->Mh)) return fail(ED_ERR_ARG, "sectors of different models");
   if (a.jz) return fail(ED_ERR_ARG, "twin sectors are not defined in the Jz basis");
   int e1, e2 = 0;
   if (a.mode == ED_MODE_NORMAL) {

@@ -19,7 +19,9 @@
 //                       restatement.
 //   seed_pair_compile   validates a plan for a (src, dst) pair of sectors by
 //                       composing seed_op_target twice per image.
-//   seed_pair_host      the kernel's arithmetic, serially in row order.
+//   seed_pair_host      the kernel's arithmetic, serially in row order
+//                       (seed_combine_host with seed_image2).
+// The (p, q) term encoding and its validation are ed_seed_plan.hpp's.
 #pragma once
 #include "ed_seed_plan.hpp"
 
@@ -53,18 +55,17 @@ ED_SEED_HD bool seed_image2(uint32_t t, PairImage im, uint32_t* source, double* 
   return true;
 }
 
-// images: [nimg][4] (lev1, op1, lev2, op2); terms: [nseed][2] image indices
-// (p, q), q < 0: the seed is image p alone.  ED_ERR_ARG unless 1 <= nimg <=
-// kPairMaxImg, 1 <= nseed <= kPairMaxSeeds, lev1 != lev2 in every image, every
-// image maps src into dst exactly (seed_op_target composed twice; the
-// intermediate quantum numbers need not belong to a sector that exists: such
-// an image never hits), no two images are the same, and every p, q is below
-// nimg with p != q.  The kernel's index tables do not bounds-check: these
-// tests keep every source row of a hit inside them.
+// images: [nimg][4] (lev1, op1, lev2, op2); terms: as seed_terms_compile
+// (ed_seed_plan.hpp) takes them.  ED_ERR_ARG unless 1 <= nimg <= kPairMaxImg,
+// lev1 != lev2 in every image, every image maps src into dst exactly
+// (seed_op_target composed twice; the intermediate quantum numbers need not
+// belong to a sector that exists: such an image never hits), no two images
+// are the same, and the terms are valid.  The kernel's index tables do not
+// bounds-check: these tests keep every source row of a hit inside them.
 inline int seed_pair_compile(const SeedSectors& S, int nimg, const int32_t* images, int nseed,
                              const int32_t* terms, PairPlan* out) {
-  if (!images || !terms || !out) return ED_ERR_ARG;
-  if (nimg < 1 || nimg > kPairMaxImg || nseed < 1 || nseed > kPairMaxSeeds) return ED_ERR_ARG;
+  if (!images || !out) return ED_ERR_ARG;
+  if (nimg < 1 || nimg > kPairMaxImg) return ED_ERR_ARG;
   PairPlan P{};
   P.nimg = nimg;
   P.nseed = nseed;
@@ -82,44 +83,20 @@ inline int seed_pair_compile(const SeedSectors& S, int nimg, const int32_t* imag
     }
     P.img[l] = PairImage{(uint8_t)im[0], (uint8_t)im[1], (uint8_t)im[2], (uint8_t)im[3]};
   }
-  for (int s = 0; s < nseed; s++) {
-    const int32_t p = terms[2 * s], q = terms[2 * s + 1];
-    if (p < 0 || p >= nimg || q >= nimg || q == p) return ED_ERR_ARG;
-    P.p[s] = (uint8_t)p;
-    P.q[s] = q < 0 ? kSeedNone : (uint8_t)q;
-  }
+  if (seed_terms_compile(nimg, nseed, kPairMaxSeeds, terms, P.p, P.q) != ED_OK) return ED_ERR_ARG;
   *out = P;
   return ED_OK;
 }
 
-// The unnormalised seeds and their norm2, serially in row order: the kernel's
-// arithmetic ((sign1 * sign2) * v_p, then + the same of q) restated on the
-// host.  x: real(8) (vc = false) or complex(8) interleaved; index(state) ->
-// 0-based row of the state in src; seeds: [nseed][dim] of the same type;
-// norm2: [nseed].
+// k_seed_pair's arithmetic ((sign1 * sign2) * v_p, then + the same of q) on
+// the host: seed_combine_host (ed_seed_plan.hpp) with seed_image2.
 template <class Index>
 inline void seed_pair_host(const PairPlan& P, int64_t dim, const uint32_t* map_dst, const double* x, bool vc,
                            Index index, double* seeds, double* norm2) {
-  const int w = vc ? 2 : 1;
-  for (int s = 0; s < P.nseed; s++) norm2[s] = 0.0;
-  for (int64_t r = 0; r < dim; r++) {
-    double u[kPairMaxImg][2];
-    for (int l = 0; l < P.nimg; l++) {
-      uint32_t src;
-      double sg;
-      u[l][0] = u[l][1] = 0.0;
-      if (!seed_image2(map_dst[r], P.img[l], &src, &sg)) continue;
-      const int64_t j = index(src);
-      for (int c = 0; c < w; c++) u[l][c] = sg * x[w * j + c];
-    }
-    for (int s = 0; s < P.nseed; s++)
-      for (int c = 0; c < w; c++) {
-        double a = u[P.p[s]][c];
-        if (P.q[s] != kSeedNone) a = a + u[P.q[s]][c];
-        seeds[((size_t)s * dim + r) * w + c] = a;
-        norm2[s] += a * a;
-      }
-  }
+  seed_combine_host<kPairMaxImg>(
+      P.nimg, P.nseed, P.p, P.q,
+      [&](uint32_t t, int l, uint32_t* src, double* sg) { return seed_image2(t, P.img[l], src, sg); }, dim, map_dst,
+      x, vc, index, seeds, norm2);
 }
 
 }  // namespace edg

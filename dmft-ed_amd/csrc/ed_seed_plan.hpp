@@ -17,8 +17,12 @@
 //                       the host restatement.
 //   seed_op_target      the sector an operator maps src into (getCsector /
 //                       getCDGsector); check_op_target in ed_hxv.hip calls it.
+//   seed_terms_compile  validates the (p, q) terms: the encoding SeedPlan and
+//                       PairPlan (ed_seed_pair.hpp) share.
 //   seed_plan_compile   validates a plan for a (src, dst) pair of sectors.
-//   seed_plan_host      the kernel's arithmetic, serially in row order.
+//   seed_combine_host   the gather kernels' arithmetic, serially in row order,
+//                       for any image functor; seed_plan_host and
+//                       seed_pair_host are its two uses.
 #pragma once
 #include <stdint.h>
 
@@ -91,15 +95,29 @@ inline int seed_op_target(const SeedSectors& S, int op, int level, int32_t* e1, 
   return ED_OK;
 }
 
-// levels / ops: [nlev]; terms: [nseed][2] image indices (p, q), q < 0: the seed
-// is image p alone.  ED_ERR_ARG unless 1 <= nlev <= kSeedMaxLev, 1 <= nseed <=
-// kSeedMaxSeeds, every image maps src into dst, the (level, op) pairs are
-// distinct, and every p, q is below nlev with p != q.  The kernel's index
+// The term encoding SeedPlan and PairPlan (ed_seed_pair.hpp) share.  terms:
+// [nseed][2] image indices (p, q), q < 0: the seed is image p alone; p, q:
+// the plan's [max_seeds] arrays.  ED_ERR_ARG unless 1 <= nseed <= max_seeds
+// and every p, q is below nimg with p != q.
+inline int seed_terms_compile(int nimg, int nseed, int max_seeds, const int32_t* terms, uint8_t* p, uint8_t* q) {
+  if (!terms || nseed < 1 || nseed > max_seeds) return ED_ERR_ARG;
+  for (int s = 0; s < nseed; s++) {
+    const int32_t ps = terms[2 * s], qs = terms[2 * s + 1];
+    if (ps < 0 || ps >= nimg || qs >= nimg || qs == ps) return ED_ERR_ARG;
+    p[s] = (uint8_t)ps;
+    q[s] = qs < 0 ? kSeedNone : (uint8_t)qs;
+  }
+  return ED_OK;
+}
+
+// levels / ops: [nlev]; terms: as seed_terms_compile takes them.  ED_ERR_ARG
+// unless 1 <= nlev <= kSeedMaxLev, every image maps src into dst, the
+// (level, op) pairs are distinct, and the terms are valid.  The kernel's index
 // tables do not bounds-check: these tests keep every source row inside them.
 inline int seed_plan_compile(const SeedSectors& S, int nlev, const int32_t* levels, const int32_t* ops,
                              int nseed, const int32_t* terms, SeedPlan* out) {
-  if (!levels || !ops || !terms || !out) return ED_ERR_ARG;
-  if (nlev < 1 || nlev > kSeedMaxLev || nseed < 1 || nseed > kSeedMaxSeeds) return ED_ERR_ARG;
+  if (!levels || !ops || !out) return ED_ERR_ARG;
+  if (nlev < 1 || nlev > kSeedMaxLev) return ED_ERR_ARG;
   SeedPlan P{};
   P.nlev = nlev;
   P.nseed = nseed;
@@ -112,43 +130,51 @@ inline int seed_plan_compile(const SeedSectors& S, int nlev, const int32_t* leve
     P.lev[l] = (uint8_t)levels[l];
     P.op[l] = (uint8_t)ops[l];
   }
-  for (int s = 0; s < nseed; s++) {
-    const int32_t p = terms[2 * s], q = terms[2 * s + 1];
-    if (p < 0 || p >= nlev || q >= nlev || q == p) return ED_ERR_ARG;
-    P.p[s] = (uint8_t)p;
-    P.q[s] = q < 0 ? kSeedNone : (uint8_t)q;
-  }
+  if (seed_terms_compile(nlev, nseed, kSeedMaxSeeds, terms, P.p, P.q) != ED_OK) return ED_ERR_ARG;
   *out = P;
   return ED_OK;
 }
 
-// The unnormalised seeds and their norm2, serially in row order: the kernel's
-// arithmetic (sg_p * v_p, then + sg_q * v_q) restated on the host.  x: real(8)
-// (vc = false) or complex(8) interleaved; index(state) -> 0-based row of the
-// state in src; seeds: [nseed][dim] of the same type; norm2: [nseed].
-template <class Index>
-inline void seed_plan_host(const SeedPlan& P, int64_t dim, const uint32_t* map_dst, const double* x, bool vc,
-                           Index index, double* seeds, double* norm2) {
+// The unnormalised seeds and their norm2, serially in row order: the gather
+// kernels' arithmetic (u_l = sign_l * v_l per image, then u_p, or u_p + u_q)
+// restated on the host.  image(t, l, &source, &sign) is the plan's image l of
+// target-row state t (false: a miss); x: real(8) (vc = false) or complex(8)
+// interleaved; index(state) -> 0-based row of the state in src; seeds:
+// [nseed][dim] of the same type; norm2: [nseed].
+template <int MaxImg, class Image, class Index>
+inline void seed_combine_host(int nimg, int nseed, const uint8_t* p, const uint8_t* q, Image image, int64_t dim,
+                              const uint32_t* map_dst, const double* x, bool vc, Index index, double* seeds,
+                              double* norm2) {
   const int w = vc ? 2 : 1;
-  for (int s = 0; s < P.nseed; s++) norm2[s] = 0.0;
+  for (int s = 0; s < nseed; s++) norm2[s] = 0.0;
   for (int64_t r = 0; r < dim; r++) {
-    double u[kSeedMaxLev][2];
-    for (int l = 0; l < P.nlev; l++) {
+    double u[MaxImg][2];
+    for (int l = 0; l < nimg; l++) {
       uint32_t src;
       double sg;
       u[l][0] = u[l][1] = 0.0;
-      if (!seed_image(map_dst[r], P.lev[l], P.op[l], &src, &sg)) continue;
+      if (!image(map_dst[r], l, &src, &sg)) continue;
       const int64_t j = index(src);
       for (int c = 0; c < w; c++) u[l][c] = sg * x[w * j + c];
     }
-    for (int s = 0; s < P.nseed; s++)
+    for (int s = 0; s < nseed; s++)
       for (int c = 0; c < w; c++) {
-        double a = u[P.p[s]][c];
-        if (P.q[s] != kSeedNone) a = a + u[P.q[s]][c];
+        double a = u[p[s]][c];
+        if (q[s] != kSeedNone) a = a + u[q[s]][c];
         seeds[((size_t)s * dim + r) * w + c] = a;
         norm2[s] += a * a;
       }
   }
+}
+
+// k_seed_plan's arithmetic (sg_p * v_p, then + sg_q * v_q) on the host.
+template <class Index>
+inline void seed_plan_host(const SeedPlan& P, int64_t dim, const uint32_t* map_dst, const double* x, bool vc,
+                           Index index, double* seeds, double* norm2) {
+  seed_combine_host<kSeedMaxLev>(
+      P.nlev, P.nseed, P.p, P.q,
+      [&](uint32_t t, int l, uint32_t* src, double* sg) { return seed_image(t, P.lev[l], P.op[l], src, sg); }, dim,
+      map_dst, x, vc, index, seeds, norm2);
 }
 
 }  // namespace edg

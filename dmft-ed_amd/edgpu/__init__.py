@@ -8,7 +8,10 @@ Modules:
               sp_lanc_eigh / sp_lanc_tridiag / sp_eigh replacements
   diag        ed_diag sector loop (single GPU) and the T=0 state list
   farm        sector farm over ranks (torch.distributed / RCCL)
-  gf          Green's functions (normal, nonSU2): device seeds, Lanczos, poles
+  gf          Green's functions (normal, nonSU2, superc): device seeds
+              (Sector.seed_batch / seed_plan when fused), Lanczos, poles;
+              seed_fractions, the one path from a seed call to the queued
+              fractions, which chi uses too
   chi         spin and density susceptibilities of the kept states: diagonal
               seeds (Sector.seed_diag), Lanczos, bosonic / tau / real-axis poles;
               pair and inter-orbital parts from two-operator seeds

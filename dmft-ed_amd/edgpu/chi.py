@@ -52,7 +52,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .diag import StateList, is_complex_vector, state_vector
-from .gf import SEED_BUFFER_BYTES, _device_vec, _dist, _peso_bz, _SectorCache, _tridiag_batch, realaxis, tridiag_poles
+from .gf import _device_vec, _dist, _peso_bz, _SectorCache, realaxis, seed_fractions
 from .params import EDConfig
 from .sectors import c_sector, cdg_sector, setup_pointers
 
@@ -100,10 +100,13 @@ def dens_pairs(cfg: EDConfig) -> List[Tuple[int, int]]:
     return [(a, b) for a in range(cfg.Norb) for b in range(a + 1, cfg.Norb)]
 
 
-def n_components(cfg: EDConfig) -> int:
+def n_components(cfg: EDConfig, pair: bool = False, exc: bool = False) -> int:
     """Flat components: spin a (Norb), spin total, density a (Norb), density
-    pair sums n_a + n_b (a < b), density total."""
-    return 2 * cfg.Norb + 2 + len(dens_pairs(cfg))
+    pair sums n_a + n_b (a < b), density total; behind them, with `pair`, Norb
+    pair components and, with `exc`, the Norb x Norb block of inter-orbital
+    ones (its diagonal is never written)."""
+    No = cfg.Norb
+    return 2 * No + 2 + len(dens_pairs(cfg)) + (No if pair else 0) + (No * No if exc else 0)
 
 
 def seed_table(cfg: EDConfig, spin: bool = True, dens: bool = True):
@@ -181,10 +184,11 @@ class Chi:
 
 
 def assemble(cfg: EDConfig, copt: ChiOptions, iv: np.ndarray, tau: np.ndarray, w: np.ndarray,
-             spin: bool = True, dens: bool = True) -> Chi:
+             spin: bool = True, dens: bool = True, pair: bool = False, exc: bool = False) -> Chi:
     """The flat component arrays (n_components, L) as a `Chi`: the spin rows as
     they are; the density diagonal from the n_a seeds, the off-diagonal from
-    the pair sums, chi[a,b] = chi[b,a] = (chi[n_a+n_b] - chi[n_a] - chi[n_b]) / 2."""
+    the pair sums, chi[a,b] = chi[b,a] = (chi[n_a+n_b] - chi[n_a] - chi[n_b]) / 2;
+    the pair rows and the inter-orbital block of the components behind them."""
     No = cfg.Norb
     out = Chi(bosonic_matsubara(copt.beta, copt.Lmats), tau_grid(copt.beta, copt.ltau),
               realaxis(copt.wini, copt.wfin, copt.Lreal))
@@ -203,14 +207,18 @@ def assemble(cfg: EDConfig, copt: ChiOptions, iv: np.ndarray, tau: np.ndarray, w
             # the total seed is built for Norb > 1 only (ED_GF_CHIDENS.f90:32-60): zero otherwise
             res.append((m, np.array(x[d0 + No + len(dens_pairs(cfg))])))
         (out.dens_iv, out.dens_tot_iv), (out.dens_tau, out.dens_tot_tau), (out.dens_w, out.dens_tot_w) = res
+    if pair:
+        p0 = pair_component(cfg, 0)
+        out.pair_iv, out.pair_tau, out.pair_w = (np.array(x[p0:p0 + No]) for x in (iv, tau, w))
+    if exc:
+        e0 = exc_component(cfg, 0, 0, pair)
+        out.exc_iv, out.exc_tau, out.exc_w = (np.array(x[e0:e0 + No * No]).reshape((No, No) + x.shape[1:])
+                                              for x in (iv, tau, w))
     return out
 
 
 # ------------------------------------------------------------ pair and inter-orbital parts
-def n_components_ext(cfg: EDConfig, pair: bool = False, exc: bool = False) -> int:
-    """`n_components` plus, behind it, Norb pair components and the Norb x Norb
-    block of inter-orbital ones (its diagonal is never written)."""
-    return n_components(cfg) + (cfg.Norb if pair else 0) + (cfg.Norb * cfg.Norb if exc else 0)
+n_components_ext, assemble_ext = n_components, assemble      # aliases: tests/test_chi_pair_cpu.py calls these names
 
 
 def pair_component(cfg: EDConfig, a: int) -> int:
@@ -263,22 +271,6 @@ def seed_pair_calls(cfg: EDConfig, pair: bool = False, exc: bool = False):
             queue.append([(("exc", a, b), exc_component(cfg, a, b, pair), +1),
                           (("exc", b, a), exc_component(cfg, b, a, pair), -1)])
         out.append((0, images, terms, queue))
-    return out
-
-
-def assemble_ext(cfg: EDConfig, copt: ChiOptions, iv: np.ndarray, tau: np.ndarray, w: np.ndarray,
-                 spin: bool = True, dens: bool = True, pair: bool = False, exc: bool = False) -> Chi:
-    """`assemble` of the leading components, then the pair rows and the
-    inter-orbital block of the components behind them."""
-    No = cfg.Norb
-    out = assemble(cfg, copt, iv, tau, w, spin=spin, dens=dens)
-    if pair:
-        p0 = pair_component(cfg, 0)
-        out.pair_iv, out.pair_tau, out.pair_w = (np.array(x[p0:p0 + No]) for x in (iv, tau, w))
-    if exc:
-        e0 = exc_component(cfg, 0, 0, pair)
-        out.exc_iv, out.exc_tau, out.exc_w = (np.array(x[e0:e0 + No * No]).reshape((No, No) + x.shape[1:])
-                                              for x in (iv, tau, w))
     return out
 
 
@@ -376,7 +368,7 @@ def build_chi(cfg: EDConfig, states: StateList, copt: Optional[ChiOptions] = Non
     calls = seed_pair_calls(cfg, pair, exc)
     vm, tg = bosonic_matsubara(copt.beta, copt.Lmats), tau_grid(copt.beta, copt.ltau)
     wr = realaxis(copt.wini, copt.wfin, copt.Lreal)
-    poles = ChiPoleSums(n_components_ext(cfg, pair, exc), vm, tg, wr, copt.beta, copt.eps, device)
+    poles = ChiPoleSums(n_components(cfg, pair, exc), vm, tg, wr, copt.beta, copt.eps, device)
     zeta = states.zeta if states.finite_t else float(states.size)
     levels = seed_levels(cfg)
     secs = setup_pointers(cfg)
@@ -391,51 +383,26 @@ def build_chi(cfg: EDConfig, states: StateList, copt: Optional[ChiOptions] = Non
             cplx = (not cfg.is_real()) or is_complex_vector(vec)
             S = cache.get(sec, True)
             x = _device_vec(vec, cplx, device)
-            nlanc = min(S.dim, copt.lanc_nGFiter)
-            # rows of one stacked buffer: SEED_BUFFER_BYTES at the most
-            step = max(1, min(len(table), SEED_BUFFER_BYTES // (S.dim * (16 if cplx else 8))))
-            for q0 in range(0, len(table), step):
-                part = table[q0:q0 + step]
-                buf, n2 = S.seed_diag(x, levels, np.array([w for _, _, w in part]))
-                keep = [q for q, v in enumerate(n2) if v != 0.0]          # norm2 == 0: no fraction
-                if not keep:
-                    continue
-                stacked = buf if len(keep) == len(part) else buf[torch.tensor(keep, device=buf.device)]
-                # the library reads the seeds on the sector's own stream
-                torch.cuda.current_stream(stacked.device).synchronize()
-                a, b, nl = _tridiag_batch(S, stacked, nlanc, not cplx, copt.threshold)
-                for row, q in enumerate(keep):
-                    name, comp, _ = part[q]
-                    # the reference diagonalises all nlanc entries (unset ones stay 0)
-                    E, z = tridiag_poles(a[row], b[row], nlanc, first_row=True)
-                    if record is not None:
-                        record.append(dict(name=name, comp=comp, state=k, isector=isec, norm2=float(n2[q]),
-                                           alfa=a[row], beta=b[row], nlanc=int(nl[row]), isign=0))
-                    poles.add(comp, _peso_bz(states, k, 1.0, float(n2[q]), zeta), states.energies[k], E, z)
+
+            def run(St, make, queue):
+                """The seeds make(rows) of sector St; queue[s]: the fractions of seed s as (name, comp, isign)."""
+                for s, norm2, a, b, nl, E, z in seed_fractions(St, make, len(queue), cplx,
+                                                               min(St.dim, copt.lanc_nGFiter), copt.threshold):
+                    for name, comp, isign in queue[s]:
+                        if record is not None:
+                            record.append(dict(name=name, comp=comp, state=k, isector=isec, norm2=norm2, alfa=a,
+                                               beta=b, nlanc=nl, isign=isign))
+                        poles.add(comp, _peso_bz(states, k, 1.0, norm2, zeta), states.energies[k], E, z, isign)
+
+            run(S, lambda rows: S.seed_diag(x, levels, np.array([table[q][2] for q in rows])),
+                [[(name, comp, 0)] for name, comp, _ in table])
             for target, images, terms, queue in calls:
                 tsec = sec if target == 0 else pair_target(cfg, sec, target)
                 if tsec is None:                                          # no such sector: no seed
                     continue
                 St = cache.get(tsec, True)
-                nlanc = min(St.dim, copt.lanc_nGFiter)
-                step = max(1, min(len(terms), SEED_BUFFER_BYTES // (St.dim * (16 if cplx else 8))))
-                for q0 in range(0, len(terms), step):
-                    buf, n2 = S.seed_pair(x, St, images, terms[q0:q0 + step])
-                    keep = [q for q, v in enumerate(n2) if v != 0.0]
-                    if not keep:
-                        continue
-                    stacked = buf if len(keep) == len(n2) else buf[torch.tensor(keep, device=buf.device)]
-                    torch.cuda.current_stream(stacked.device).synchronize()
-                    a, b, nl = _tridiag_batch(St, stacked, nlanc, not cplx, copt.threshold)
-                    for row, q in enumerate(keep):
-                        E, z = tridiag_poles(a[row], b[row], nlanc, first_row=True)
-                        for name, comp, isign in queue[q0 + q]:
-                            if record is not None:
-                                record.append(dict(name=name, comp=comp, state=k, isector=isec, norm2=float(n2[q]),
-                                                   alfa=a[row], beta=b[row], nlanc=int(nl[row]), isign=isign))
-                            poles.add(comp, _peso_bz(states, k, 1.0, float(n2[q]), zeta), states.energies[k], E, z,
-                                      isign)
+                run(St, lambda rows: S.seed_pair(x, St, images, [terms[q] for q in rows]), queue)
     finally:
         cache.close()
     poles.flush()
-    return assemble_ext(cfg, copt, *poles.to_host(), spin=spin, dens=dens, pair=pair, exc=exc)
+    return assemble(cfg, copt, *poles.to_host(), spin=spin, dens=dens, pair=pair, exc=exc)

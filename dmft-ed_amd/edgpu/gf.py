@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -293,13 +293,36 @@ def orbital_pairs(cfg: EDConfig):
     return out
 
 
+class Seed(NamedTuple):
+    """A seed spec: sum_t coef_t op_t|gs> over `terms`, rows (level, coef) with
+    the seed's `op` (0 c, 1 c^+) or (level, coef, op_t) with their own; `ispin`
+    is the spin of the first level, `weight` multiplies norm2 in the pole sum."""
+
+    op: int
+    isign: int
+    ispin: int
+    terms: list
+    weight: complex
+
+
+class Job(NamedTuple):
+    """One continued fraction: component `comp` of G, the channel `tag`, kept
+    state `k`, its seed, and the sectors of the kept state and of the seed."""
+
+    comp: object
+    tag: tuple
+    k: int
+    seed: Seed
+    src: object
+    dst: object
+
+
 def _job_list(cfg: EDConfig, states: StateList, orbital_mix: bool = True):
-    """Every (component, kept state, seed spec) of build_gf in the serial
-    accumulation order: diagonal components (ispin, iorb), then for nonSU2 the
-    mixed seeds (ispin != jspin, iorb), then (normal mode, hybrid / replica
-    bath, `orbital_mix`) the orbital-mixed seeds (ispin, iorb < jorb) of
-    lanc_build_gf_normal_mix_c.  A component is (ispin, jspin, iorb, jorb); a
-    seed spec is (op, isign, spin of the first level, [(level, coef)], weight)."""
+    """Every `Job` of build_gf in the serial accumulation order: diagonal
+    components (ispin, iorb), then for nonSU2 the mixed seeds (ispin != jspin,
+    iorb), then (normal mode, hybrid / replica bath, `orbital_mix`) the
+    orbital-mixed seeds (ispin, iorb < jorb) of lanc_build_gf_normal_mix_c.  A
+    component is (ispin, jspin, iorb, jorb)."""
     Ns, No, Nsp = cfg.Ns, cfg.Norb, cfg.Nspin
     site = lambda o, s: o + s * Ns          # impIndex(iorb,ispin), 0-based bit
     chans = []
@@ -342,7 +365,7 @@ def _job_list(cfg: EDConfig, states: StateList, orbital_mix: bool = True):
             for spec in seeds:
                 jsec = _target(cfg, sec, spec[0], spec[2], comp[2])
                 if jsec is not None:
-                    jobs.append((comp, tag, k, spec, sec, jsec))
+                    jobs.append(Job(comp, tag, k, Seed(*spec), sec, jsec))
     return jobs, pairs
 
 
@@ -350,13 +373,13 @@ SUPERC_CHANNELS = 3      # auxGmats(1:3,:): G_aa, barG_aa, A_aa (ED_GF_SUPERC.f9
 
 
 def _job_list_superc(cfg: EDConfig, states: StateList):
-    """Every (component, kept state, seed spec) of lanc_build_gf_superc_c
-    (ED_GF_SUPERC.f90:88-446) in the order in which each aux channel
-    accumulates: orbital, kept state, then the six seeds.  A component is the
-    flat index iorb * 3 + channel (channel 0: G_aa, 1: barG_aa, 2: A_aa); a
-    seed spec is (op of the first term, isign, 0, [(level, 1, op)], 1.0): every
-    term carries its own operator type.  c+_up and c_dw raise sz by one, c_up
-    and c+_dw lower it; a seed whose target sector does not exist is left out."""
+    """Every `Job` of lanc_build_gf_superc_c (ED_GF_SUPERC.f90:88-446) in the
+    order in which each aux channel accumulates: orbital, kept state, then the
+    six seeds.  A component is the flat index iorb * 3 + channel (channel 0:
+    G_aa, 1: barG_aa, 2: A_aa); a seed is Seed(op of the first term, isign, 0,
+    [(level, 1, op)], 1.0): every term carries its own operator type.  c+_up
+    and c_dw raise sz by one, c_up and c+_dw lower it; a seed whose target
+    sector does not exist is left out."""
     Ns = cfg.Ns
     secs = setup_pointers(cfg)
     by_sz = {s.q1: s for s in secs}
@@ -376,8 +399,8 @@ def _job_list_superc(cfg: EDConfig, states: StateList):
             for chan, dsz, isign, terms in seeds:
                 jsec = by_sz.get(sec.q1 + dsz)
                 if jsec is not None:
-                    jobs.append((iorb * SUPERC_CHANNELS + chan, ("superc", chan, iorb), k,
-                                 (terms[0][2], isign, 0, terms, 1.0), sec, jsec))
+                    jobs.append(Job(iorb * SUPERC_CHANNELS + chan, ("superc", chan, iorb), k,
+                                    Seed(terms[0][2], isign, 0, terms, 1.0), sec, jsec))
     return jobs
 
 
@@ -490,111 +513,90 @@ def _device_vec(vec, cplx: bool, device: int):
     return vec.to(device=f"cuda:{device}", dtype=dt).contiguous()
 
 
-def _seed_calls(jobs, members):
-    """Split `members` (jobs of one target sector and vector type) into
-    ed_sector_seed_batch calls: the same kept state and operator type, at most
-    SEED_MAX_SEEDS seeds and SEED_MAX_LEVELS distinct levels.  Yields
-    (k, op, levels, members of the call)."""
+def _seed_calls(jobs, members, mixed: bool):
+    """Split `members` (jobs of one target sector and vector type) into fused
+    seed calls of at most SEED_MAX_SEEDS seeds and SEED_MAX_LEVELS distinct
+    images.  An image is a level and the calls are per (kept state, operator
+    type) for ed_sector_seed_batch; `mixed` (terms with their own operator
+    type, ed_sector_seed_plan): an image is (level, op) and the calls are per
+    kept state.  Yields (k, op or None, images, members of the call)."""
+    image = (lambda t: (t[0], t[2])) if mixed else (lambda t: t[0])
     by = {}
     for n in members:
-        by.setdefault((jobs[n][2], jobs[n][3][0]), []).append(n)
+        by.setdefault((jobs[n].k, None if mixed else jobs[n].seed.op), []).append(n)
     for (k, op), ns in by.items():
-        levels, call = [], []
-        for n in ns:
-            new = [lv for lv, _ in jobs[n][3][3] if lv not in levels]
-            if call and (len(call) == SEED_MAX_SEEDS or len(levels) + len(new) > SEED_MAX_LEVELS):
-                yield k, op, levels, call
-                levels, call = [], []
-                new = list(dict.fromkeys(lv for lv, _ in jobs[n][3][3]))
-            levels += new
-            call.append(n)
-        yield k, op, levels, call
-
-
-def _fused_seeds(cfg, states, jobs, members, cache, cplx: bool):
-    """The normalised seeds of `members` as rows of one device tensor, and
-    their norm2, from ed_sector_seed_batch (csrc/ed_seed.hpp): one call per
-    (kept state, operator type).  Returns (members in row order, tensor, norm2)."""
-    import torch
-
-    HJ = cache.get(jobs[members[0]][5], True)
-    dt = torch.complex128 if cplx else torch.float64
-    out = torch.empty((len(members), HJ.dim), dtype=dt, device=f"cuda:{cache.device}")
-    st = torch.cuda.current_stream(out.device)
-    P = ctypes.c_void_p
-    rows, norms, r0 = [], [], 0
-    for k, op, levels, call in _seed_calls(jobs, members):
-        HI = cache.get(jobs[call[0]][4], False)
-        x = _device_vec(_state_vec(cfg, states, k, cache), cplx, cache.device)
-        coef = np.zeros((len(call), len(levels)), dtype=np.complex128)
-        for q, n in enumerate(call):
-            for lv, c in jobs[n][3][3]:
-                coef[q, levels.index(lv)] = c
-        lev = np.array(levels, dtype=np.int32)
-        n2 = np.zeros(len(call))
-        check(_lib.load().ed_sector_seed_batch(HI.handle, HJ.handle, op, len(levels), P(lev.ctypes.data),
-                                               len(call), P(coef.ctypes.data), 1 if cplx else 0,
-                                               P(x.data_ptr()), P(out[r0].data_ptr()), P(n2.ctypes.data),
-                                               P(st.cuda_stream)), "ed_sector_seed_batch")
-        rows += call
-        norms += list(n2)
-        r0 += len(call)
-    return rows, out, norms
-
-
-def _plan_calls(jobs, members):
-    """Split `members` (jobs of one target sector and vector type whose terms
-    carry their own operator type) into ed_sector_seed_plan calls: the same
-    kept state, at most SEED_MAX_SEEDS seeds and SEED_MAX_LEVELS distinct
-    (level, op) images.  Yields (k, images, members of the call)."""
-    by = {}
-    for n in members:
-        by.setdefault(jobs[n][2], []).append(n)
-    for k, ns in by.items():
         images, call = [], []
         for n in ns:
-            mine = list(dict.fromkeys((lv, o) for lv, _, o in jobs[n][3][3]))
+            mine = list(dict.fromkeys(image(t) for t in jobs[n].seed.terms))
             new = [im for im in mine if im not in images]
             if call and (len(call) == SEED_MAX_SEEDS or len(images) + len(new) > SEED_MAX_LEVELS):
-                yield k, images, call
+                yield k, op, images, call
                 images, call, new = [], [], mine
             images += new
             call.append(n)
-        yield k, images, call
+        yield k, op, images, call
 
 
-def _fused_seeds_plan(cfg, states, jobs, members, cache, cplx: bool):
-    """_fused_seeds for seeds whose images mix operator types (superc): one
-    ed_sector_seed_plan call (k_seed_plan, csrc/ed_seed.hpp) per kept state.
-    Returns (members in row order, tensor, norm2)."""
+def _fused_seeds(cfg, states, jobs, members, cache, cplx: bool, mixed: bool = False):
+    """The normalised seeds of `members` as rows of one device tensor, and
+    their norm2, one `_seed_calls` call after the other: Sector.seed_batch
+    (k_seed_gather, csrc/ed_seed.hpp), or with `mixed` Sector.seed_plan
+    (k_seed_plan).  Returns (members in row order, tensor, norm2)."""
     import torch
 
-    HJ = cache.get(jobs[members[0]][5], True)
+    HJ = cache.get(jobs[members[0]].dst, True)
     dt = torch.complex128 if cplx else torch.float64
     out = torch.empty((len(members), HJ.dim), dtype=dt, device=f"cuda:{cache.device}")
-    st = torch.cuda.current_stream(out.device)
-    P = ctypes.c_void_p
-    rows, norms, r0 = [], [], 0
-    for k, images, call in _plan_calls(jobs, members):
-        HI = cache.get(jobs[call[0]][4], False)
+    rows, norms = [], []
+    for k, op, images, call in _seed_calls(jobs, members, mixed):
+        HI = cache.get(jobs[call[0]].src, False)
         x = _device_vec(_state_vec(cfg, states, k, cache), cplx, cache.device)
-        lev = np.array([lv for lv, _ in images], dtype=np.int32)
-        ops = np.array([o for _, o in images], dtype=np.int32)
-        terms = np.full((len(call), 2), -1, dtype=np.int32)
-        for s, n in enumerate(call):
-            tt = jobs[n][3][3]
-            assert len(tt) <= 2 and all(c == 1 for _, c, _ in tt)     # unit coefficients: all superc needs
-            for j, (lv, _, o) in enumerate(tt):
-                terms[s, j] = images.index((lv, o))
-        n2 = np.zeros(len(call))
-        check(_lib.load().ed_sector_seed_plan(HI.handle, HJ.handle, len(images), P(lev.ctypes.data),
-                                              P(ops.ctypes.data), len(call), P(terms.ctypes.data),
-                                              1 if cplx else 0, P(x.data_ptr()), P(out[r0].data_ptr()),
-                                              P(n2.ctypes.data), P(st.cuda_stream)), "ed_sector_seed_plan")
+        into = out[len(rows):len(rows) + len(call)]
+        if mixed:
+            terms = np.full((len(call), 2), -1, dtype=np.int32)
+            for s, n in enumerate(call):
+                tt = jobs[n].seed.terms
+                assert len(tt) <= 2 and all(c == 1 for _, c, _ in tt)     # unit coefficients: all superc needs
+                for j, (lv, _, o) in enumerate(tt):
+                    terms[s, j] = images.index((lv, o))
+            _, n2 = HI.seed_plan(x, HJ, [lv for lv, _ in images], [o for _, o in images], terms, out=into)
+        else:
+            coef = np.zeros((len(call), len(images)), dtype=np.complex128)
+            for q, n in enumerate(call):
+                for lv, c in jobs[n].seed.terms:
+                    coef[q, images.index(lv)] = c
+            _, n2 = HI.seed_batch(x, HJ, op, images, coef, out=into)
         rows += call
         norms += list(n2)
-        r0 += len(call)
     return rows, out, norms
+
+
+def seed_fractions(S: Sector, make, nseed: int, cplx: bool, nlanc: int, threshold: float, chunked: bool = True):
+    """From seed calls to continued fractions, for build_gf, build_gf_superc
+    and build_chi.  make(rows) -> (device tensor, norm2) builds the normalised
+    seeds `rows` (a range of 0..nseed-1) of sector S as the tensor's rows;
+    `chunked`: a tensor stays under SEED_BUFFER_BYTES.  Seeds with norm2 == 0
+    are dropped (no fraction), the others of a tensor tridiagonalised in one
+    batched launch.  Yields (seed index, norm2, alfa, beta, nlanc found, E, z)
+    in seed order, E and z(1, j) from `tridiag_poles` over all `nlanc` entries
+    (the reference diagonalises them all; unset ones stay 0)."""
+    import torch
+
+    step = max(1, SEED_BUFFER_BYTES // (S.dim * (16 if cplx else 8))) if chunked else max(1, nseed)
+    for q0 in range(0, nseed, step):
+        rows = range(q0, min(q0 + step, nseed))
+        buf, n2 = make(rows)
+        keep = [q for q, v in enumerate(n2) if v != 0.0]
+        if not keep:
+            continue
+        stacked = buf if len(keep) == len(rows) else buf[torch.tensor(keep, device=buf.device)]
+        # the library reads the seeds on the sector's own (non-blocking) stream:
+        # what torch's stream still does to them must be complete first
+        torch.cuda.current_stream(stacked.device).synchronize()
+        a, b, nl = _tridiag_batch(S, stacked, nlanc, not cplx, threshold)
+        for row, q in enumerate(keep):
+            E, z = tridiag_poles(a[row], b[row], nlanc, first_row=True)
+            yield q0 + q, float(n2[q]), a[row], b[row], int(nl[row]), E, z
 
 
 def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record=None):
@@ -608,58 +610,41 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
     cache = _SectorCache(cfg, gopt, device)
     groups = {}
     for n in todo:
-        comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
-        p = states.partner(k)
-        vec = states.vectors[k if p is None else p]    # a twin's vector has its partner's type
+        p = states.partner(jobs[n].k)
+        vec = states.vectors[jobs[n].k if p is None else p]    # a twin's vector has its partner's type
         if vec is None:
             raise ValueError("the Green's function needs the state vectors (keep_vectors=True)")
-        cplx = (not cfg.is_real()) or is_complex_vector(vec) or any(np.imag(t[1]) != 0 for t in terms)
-        groups.setdefault((jsec.q1, jsec.q2, cplx), []).append(n)
+        cplx = (not cfg.is_real()) or is_complex_vector(vec) or any(np.imag(t[1]) != 0 for t in jobs[n].seed.terms)
+        groups.setdefault((jobs[n].dst.q1, jobs[n].dst.q2, cplx), []).append(n)
     fracs = {}
     try:
         for (_, _, cplx), members in groups.items():
-            chunks = [members]
-            if gopt.fused_seeds:
-                # rows of one stacked buffer: SEED_BUFFER_BYTES at the most
-                step = max(1, SEED_BUFFER_BYTES // (jobs[members[0]][5].dim * (16 if cplx else 8)))
-                chunks = [members[i:i + step] for i in range(0, len(members), step)]
-            for chunk in chunks:
-                live, seeds, norms = [], [], []
+            HJ = cache.get(jobs[members[0]].dst, True)
+            held = {}                                  # row of the group -> job
+
+            def make(rows):
+                chunk = [members[i] for i in rows]
                 if gopt.fused_seeds:
-                    fuse = _fused_seeds_plan if cfg.ed_mode == "superc" else _fused_seeds
-                    rows, buf, n2 = fuse(cfg, states, jobs, chunk, cache, cplx)
-                    keep = [q for q, v in enumerate(n2) if v != 0.0]    # norm2 == 0: no fraction
-                    live, norms = [rows[q] for q in keep], [float(n2[q]) for q in keep]
-                    if not live:
-                        continue
-                    stacked = buf if len(keep) == len(rows) else buf[torch.tensor(keep, device=buf.device)]
+                    order, buf, n2 = _fused_seeds(cfg, states, jobs, chunk, cache, cplx, cfg.ed_mode == "superc")
                 else:
-                    for n in chunk:
-                        comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
-                        HI, HJ = cache.get(sec, False), cache.get(jsec, True)
-                        seed, norm2 = _seed(HI, HJ, op, terms, _state_vec(cfg, states, k, cache), cplx)
-                        if norm2 == 0.0:
-                            continue
-                        live.append(n)
-                        seeds.append(seed)
-                        norms.append(norm2)
-                    if not live:
-                        continue
-                    stacked = torch.stack(seeds).contiguous()
-                HJ = cache.get(jobs[live[0]][5], True)
-                nlanc = min(HJ.dim, gopt.lanc_nGFiter)
-                # the library copies the seeds on the sector's own (non-blocking)
-                # stream: the stack kernel on torch's stream must be complete first
-                torch.cuda.current_stream(stacked.device).synchronize()
-                a, b, nl = _tridiag_batch(HJ, stacked, nlanc, not cplx, gopt.threshold)
-                for q, n in enumerate(live):
-                    comp, tag, k, (op, isign, ispin, terms, weight), sec, jsec = jobs[n]
-                    E, z = tridiag_poles(a[q], b[q], nlanc, first_row=True)
-                    if record is not None:
-                        record.append((n, dict(channel=tag, isector=states.sectors[k], op=op, norm2=norms[q],
-                                               alfa=a[q], beta=b[q], nlanc=int(nl[q]))))
-                    fracs[n] = (comp, _peso(cfg)(states, k, weight, norms[q], zeta), states.energies[k], E, z,
-                                isign)
+                    order = chunk
+                    made = [_seed(cache.get(jobs[n].src, False), HJ, jobs[n].seed.op, jobs[n].seed.terms,
+                                  _state_vec(cfg, states, jobs[n].k, cache), cplx) for n in chunk]
+                    buf, n2 = torch.stack([y for y, _ in made]).contiguous(), [v for _, v in made]
+                held.update(zip(rows, order))
+                return buf, n2
+
+            nlanc = min(HJ.dim, gopt.lanc_nGFiter)
+            # only the fused seeds are chunked: the others exist one by one before they are stacked
+            for i, norm2, a, b, nl, E, z in seed_fractions(HJ, make, len(members), cplx, nlanc, gopt.threshold,
+                                                           chunked=gopt.fused_seeds):
+                n = held[i]
+                job = jobs[n]
+                if record is not None:
+                    record.append((n, dict(channel=job.tag, isector=states.sectors[job.k], op=job.seed.op,
+                                           norm2=norm2, alfa=a, beta=b, nlanc=nl)))
+                fracs[n] = (job.comp, _peso(cfg)(states, job.k, job.seed.weight, norm2, zeta),
+                            states.energies[job.k], E, z, job.seed.isign)
     finally:
         cache.close()
     for n in todo:
@@ -697,7 +682,7 @@ def _run_jobs_threaded(cfg, states, gopt, jobs, todo, device, poles, zeta):
         _run_job(cfg, states, gopt, jobs[n], local.cache, r, None, zeta)
         return r.q
 
-    order = sorted(todo, key=lambda n: -jobs[n][5].dim)   # longest first
+    order = sorted(todo, key=lambda n: -jobs[n].dst.dim)   # longest first
     try:
         with ThreadPoolExecutor(max_workers=min(gopt.workers, len(todo)), initializer=init) as ex:
             futs = {n: ex.submit(work, n) for n in order}
@@ -755,7 +740,7 @@ def _sum_jobs(cfg, states, gopt, jobs, Gm, Gr, device, record, runner, who: str,
     if world > 1:
         from .farm import lpt_partition
 
-        costs = [float(min(j[5].dim, gopt.lanc_nGFiter)) * j[5].dim for j in jobs]
+        costs = [float(min(j.dst.dim, gopt.lanc_nGFiter)) * j.dst.dim for j in jobs]
         mine = set(lpt_partition(costs, world)[rank])
     else:
         mine = set(range(len(jobs)))
@@ -781,7 +766,7 @@ def _sum_jobs(cfg, states, gopt, jobs, Gm, Gr, device, record, runner, who: str,
                 if runner is None:
                     _run_job(cfg, states, gopt, job, cache, poles, record, zeta)
                 else:
-                    runner(cfg, states, gopt, job, wm, wr, Gm[job[0]], Gr[job[0]], zeta)
+                    runner(cfg, states, gopt, job, wm, wr, Gm[job.comp], Gr[job.comp], zeta)
         finally:
             cache.close()
     if poles is not None:

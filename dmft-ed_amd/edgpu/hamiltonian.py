@@ -320,23 +320,61 @@ class Sector:
                                            _ptr(out), _stream_ptr(st)), "ed_sector_expect")
         return out[0::2] + 1j * out[1::2]
 
-    # ------------------------------------------------- susceptibility seeds
+    # ------------------------------------------------- fused seeds
+    # One shape for the four seed calls: `vec` lives in this sector, `dst` is
+    # the sector every image maps it into; returns (device tensor
+    # (nseed, dst.dim) of the vector's type, norm2 (nseed,)), the seeds
+    # normalised and a seed with norm2 == 0 all zero.  out: a contiguous
+    # device tensor of that shape and type to write into.
+    def _seed_args(self, what, vec, dst: "Sector", nseed, out):
+        vt, x, st = self._state_arg(vec)
+        if dst.device != self.device:
+            raise ValueError(f"{what}: sectors on different devices")
+        if out is None:
+            out = self._out_array((nseed, dst.dim), vt, True)
+        elif tuple(out.shape) != (nseed, dst.dim) or out.dtype != x.dtype or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous (nseed, dst.dim) tensor of the vector's type")
+        return vt, x, st, out, np.zeros(nseed)
+
+    def seed_batch(self, vec, dst: "Sector", op: int, levels, coef, out=None):
+        """Green's-function seeds of one operator type (ed_sector_seed_batch):
+        seeds[q] = sum_l coef[q][l] * op_{levels[l]} |vec>, op 0 = c and
+        1 = c^+ on the 0-based bit; coef: (nseed, nlev) complex, (0, 0) for a
+        level the seed does not use.  The vvinit loops of
+        ED_GF_NORMAL.f90:159-174 and :312-344."""
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        cf = np.ascontiguousarray(coef, dtype=np.complex128).reshape(-1, len(lv))
+        vt, x, st, out, n2 = self._seed_args("seed_batch", vec, dst, cf.shape[0], out)
+        check(_lib.load().ed_sector_seed_batch(self._h, dst.handle, op, len(lv), _ptr(lv), cf.shape[0], _ptr(cf), vt,
+                                               _tptr(x), _tptr(out), _ptr(n2), _stream_ptr(st)),
+              "ed_sector_seed_batch")
+        return out, n2
+
+    def seed_plan(self, vec, dst: "Sector", levels, ops, terms, out=None):
+        """Seeds whose images mix operator types (ed_sector_seed_plan): image
+        l is ops[l] on levels[l] of |vec>; terms: rows (p, q) of image
+        indices, q < 0 for image p alone.  The vvinit loops of
+        lanc_build_gf_superc_c (ED_GF_SUPERC.f90:119-439)."""
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        op = np.ascontiguousarray(ops, dtype=np.int32)
+        tm = np.ascontiguousarray(terms, dtype=np.int32).reshape(-1, 2)
+        if len(op) != len(lv):
+            raise ValueError("seed_plan: one operator type per level")
+        vt, x, st, out, n2 = self._seed_args("seed_plan", vec, dst, tm.shape[0], out)
+        check(_lib.load().ed_sector_seed_plan(self._h, dst.handle, len(lv), _ptr(lv), _ptr(op), tm.shape[0], _ptr(tm),
+                                              vt, _tptr(x), _tptr(out), _ptr(n2), _stream_ptr(st)),
+              "ed_sector_seed_plan")
+        return out, n2
+
     def seed_diag(self, vec, levels, weights, out=None):
         """Seeds of operators diagonal in the Fock basis (ed_sector_seed_diag):
         seeds[q][r] = (sum_l weights[q][l] * bit(map[r], levels[l])) * vec[r],
         normalised, for a state vector of this sector; the vvinit loops of
         the susceptibility builders (ED_GF_CHISPIN.f90:98-103,
-        ED_GF_CHIDENS.f90:127-132).  Returns (device tensor (nseed, dim) of the
-        vector's type, norm2 (nseed,)); a seed with norm2 == 0 is all zero.
-        out: a contiguous device tensor of that shape and type to write into."""
+        ED_GF_CHIDENS.f90:127-132).  The seeds stay in this sector."""
         lv = np.ascontiguousarray(levels, dtype=np.int32)
         w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1, len(lv))
-        vt, x, st = self._state_arg(vec)
-        if out is None:
-            out = self._out_array((w.shape[0], self.dim), vt, True)
-        elif tuple(out.shape) != (w.shape[0], self.dim) or out.dtype != x.dtype or not out.is_contiguous():
-            raise ValueError("seed_diag: out must be a contiguous (nseed, dim) tensor of the vector's type")
-        n2 = np.zeros(w.shape[0])
+        vt, x, st, out, n2 = self._seed_args("seed_diag", vec, self, w.shape[0], out)
         check(_lib.load().ed_sector_seed_diag(self._h, len(lv), _ptr(lv), w.shape[0], _ptr(w), vt, _tptr(x),
                                               _tptr(out), _ptr(n2), _stream_ptr(st)), "ed_sector_seed_diag")
         return out, n2
@@ -349,20 +387,10 @@ class Sector:
         on lev1 acting first; terms: rows (p, q) of image indices, q < 0 for
         image p alone.  The vvinit loops of the pair susceptibility
         (ED_GF_CHIPAIR.f90:98-102, :144-148) and of the inter-orbital density
-        susceptibility (ED_GF_CHIDENS.f90:523-586, :596-659).  Returns (device
-        tensor (nseed, dst.dim) of the vector's type, norm2 (nseed,)); a seed
-        with norm2 == 0 is all zero.  out: a contiguous device tensor of that
-        shape and type to write into."""
+        susceptibility (ED_GF_CHIDENS.f90:523-586, :596-659)."""
         im = np.ascontiguousarray(images, dtype=np.int32).reshape(-1, 4)
         tm = np.ascontiguousarray(terms, dtype=np.int32).reshape(-1, 2)
-        vt, x, st = self._state_arg(vec)
-        if dst.device != self.device:
-            raise ValueError("seed_pair: sectors on different devices")
-        if out is None:
-            out = self._out_array((tm.shape[0], dst.dim), vt, True)
-        elif tuple(out.shape) != (tm.shape[0], dst.dim) or out.dtype != x.dtype or not out.is_contiguous():
-            raise ValueError("seed_pair: out must be a contiguous (nseed, dst.dim) tensor of the vector's type")
-        n2 = np.zeros(tm.shape[0])
+        vt, x, st, out, n2 = self._seed_args("seed_pair", vec, dst, tm.shape[0], out)
         check(_lib.load().ed_sector_seed_pair(self._h, dst.handle, im.shape[0], _ptr(im), tm.shape[0], _ptr(tm), vt,
                                               _tptr(x), _tptr(out), _ptr(n2), _stream_ptr(st)), "ed_sector_seed_pair")
         return out, n2

@@ -364,8 +364,14 @@ int ed_sector_apply_op_acc(const ed_sector* src, const ed_sector* dst, int32_t o
  * gives the unnormalised values of ed_sector_apply_op + ed_sector_apply_op_acc
  * bit for bit.  seeds: device, [nseed][dst->dim], written whole (no memset
  * needed).  The norms are summed in a fixed order: two calls on the same
- * input return the same bits.  Row-split sectors: ED_ERR_UNSUPPORTED.
- * Synchronous on `stream` (norm2 is a host result). */
+ * input return the same bits.  Synchronous on `stream` (norm2 is a host
+ * result).
+ * The four ed_sector_seed_* entries share these checks, all made before
+ * anything is launched, so a refused call leaves seeds and norm2 untouched:
+ * ED_ERR_ARG unless the pointers are non-null, vtype is 0 or 1, the sectors
+ * are on one device and of one model, and seeds does not overlap src_vec
+ * (the kernels read src_vec while they store seeds); ED_ERR_UNSUPPORTED for
+ * a row-split sector. */
 int ed_sector_seed_batch(const ed_sector* src, const ed_sector* dst, int32_t op,
                          int32_t nlev, const int32_t* levels,
                          int32_t nseed, const double* coef,
@@ -382,9 +388,9 @@ int ed_sector_seed_batch(const ed_sector* src, const ed_sector* dst, int32_t op,
  * ed_sector_apply_op + ed_sector_apply_op_acc(coef = 1).  ED_ERR_ARG, before
  * anything is launched, unless 1 <= nlev <= 2*ED_MAX_NORB, 1 <= nseed <= 32,
  * every image maps src into dst (as ed_sector_apply_op), the (level, op) pairs
- * are distinct, every index is below nlev and the two of a seed differ, and
- * vtype is 0 or 1.  seeds, norm2, determinism, row-split sectors and
- * synchronisation as ed_sector_seed_batch. */
+ * are distinct, every index is below nlev and the two of a seed differ.
+ * seeds, norm2, determinism, the shared checks and synchronisation as
+ * ed_sector_seed_batch. */
 int ed_sector_seed_plan(const ed_sector* src, const ed_sector* dst,
                         int32_t nlev, const int32_t* levels, const int32_t* ops,
                         int32_t nseed, const int32_t* terms,
@@ -400,11 +406,10 @@ int ed_sector_seed_plan(const ed_sector* src, const ed_sector* dst,
  * stays in the sector of src_vec: any whole sector, stored or direct, of any
  * ed_mode and of the Jz basis.  ED_ERR_ARG, before anything is launched,
  * unless 1 <= nlev <= 2*ED_MAX_NORB, the levels are distinct 0-based bits
- * below 2*Ns, 1 <= nseed <= 32, vtype is 0 or 1 and seeds does not overlap
- * src_vec.  weight: [nseed][nlev] real, host.  seeds: device, [nseed][dim],
- * written whole (no memset needed).  The norms are summed in a fixed order:
- * two calls on the same input return the same bits.  Row-split sectors:
- * ED_ERR_UNSUPPORTED.  Synchronous on `stream` (norm2 is a host result). */
+ * below 2*Ns and 1 <= nseed <= 32.  weight: [nseed][nlev] real, host.  seeds:
+ * device, [nseed][dim], written whole (no memset needed).  norm2,
+ * determinism, the shared checks and synchronisation as
+ * ed_sector_seed_batch. */
 int ed_sector_seed_diag(const ed_sector* s, int32_t nlev, const int32_t* levels,
                         int32_t nseed, const double* weight,
                         int32_t vtype, const void* src_vec,
@@ -423,10 +428,9 @@ int ed_sector_seed_diag(const ed_sector* s, int32_t nlev, const int32_t* levels,
  * by ed_sector_apply_op_acc(coef = 1).  src == dst is allowed.  ED_ERR_ARG,
  * before anything is launched, unless 1 <= nimg <= 12, 1 <= nseed <= 12,
  * lev1 != lev2, every image maps src into dst exactly, no two images are the
- * same, every index is below nimg and the two of a seed differ, the sectors
- * are on one device and of one model, vtype is 0 or 1 and seeds does not
- * overlap src_vec.  seeds ([nseed][dst->dim]), norm2, determinism, row-split
- * sectors and synchronisation as ed_sector_seed_batch. */
+ * same, every index is below nimg and the two of a seed differ.  seeds
+ * ([nseed][dst->dim]), norm2, determinism, the shared checks and
+ * synchronisation as ed_sector_seed_batch. */
 int ed_sector_seed_pair(const ed_sector* src, const ed_sector* dst,
                         int32_t nimg, const int32_t* images,
                         int32_t nseed, const int32_t* terms,

@@ -39,19 +39,25 @@ def _cdiv(pr, a, b):
 
 
 def chi_poles_host(fracs, beta, vm, tau, wr, eps, ncomp, start=None):
-    """fracs: (comp, peso, Ei, E, z) in queue order.  Returns (iv, tau, w,
-    (sum |terms| of iv, tau, w)) — the arrays start from `start` = (iv, tau, w)
-    (a second flush) or zero."""
+    """fracs: (comp, peso, Ei, E, z) or (comp, peso, Ei, E, z, isign) in queue
+    order; isign 0 (both branches, the default), +1 or -1: the selector of
+    ed_chi_add_poles_signed, the branch that is not selected left out.  Returns
+    (iv, tau, w, (sum |terms| of iv, tau, w)) — the arrays start from `start` =
+    (iv, tau, w) (a second flush) or zero."""
     vm, tau, wr = (np.asarray(x, float) for x in (vm, tau, wr))
     civ = np.zeros((ncomp, len(vm)), complex) if start is None else np.array(start[0])
     ctau = np.zeros((ncomp, len(tau))) if start is None else np.array(start[1])
     cw = np.zeros((ncomp, len(wr)), complex) if start is None else np.array(start[2])
     mag = [np.abs(civ), np.abs(ctau), np.abs(cw)]
     tm = beta - tau
-    for comp, peso, ei, E, z in fracs:
+    for comp, peso, ei, E, z, *sel in fracs:
+        isign = sel[0] if sel else 0
+        assert isign in (0, 1, -1)
         E, z = np.asarray(E, float), np.asarray(z, float)
         f, s = thermal_host(beta, E - ei)
         for sg in (0, 1):                      # isign = +1, then -1
+            if isign == (1 if sg else -1):     # a one-sign fraction: the other branch is not its
+                continue
             for j in range(len(E)):
                 de = E[j] - ei
                 pj = (peso * z[j]) * z[j]

@@ -7,17 +7,17 @@ forward_image          one image op2_lev2 op1_lev1 |x> in the FORWARD form: over
                        reference), scattered into the target sector's rows.
                        The kernel and csrc/ed_seed_pair.hpp run the gather form.
 numpy_pair_seeds       the unnormalised seeds of ed_sector_seed_pair from it.
-chi_poles_host_signed  chi_host.chi_poles_host with the isign selector of
-                       ed_chi_add_poles_signed: the same formulas in the same
-                       order, the branch that is not selected left out.
+chi_poles_host_signed  chi_host.chi_poles_host under the name these tests
+                       use: fractions carry the isign selector of
+                       ed_chi_add_poles_signed.
 replay_chi_pair        build_chi(spin=False, dens=False, pair, exc) with every
                        device piece replaced: numpy seeds, the oracle's plain
                        Lanczos, `tridiag_poles`, chi_poles_host_signed.
 """
 import numpy as np
 
-from chi_host import _cdiv, thermal_host
-from edgpu.chi import (assemble_ext, bosonic_matsubara, n_components_ext, pair_target, seed_pair_calls, tau_grid)
+from chi_host import chi_poles_host
+from edgpu.chi import assemble, bosonic_matsubara, n_components, pair_target, seed_pair_calls, tau_grid
 from edgpu.gf import _peso_bz, realaxis, tridiag_poles
 from edgpu.sectors import setup_pointers
 
@@ -59,41 +59,7 @@ def numpy_pair_seeds(map_src, map_dst, images, terms, x):
     return np.array([img[p] if q < 0 else img[p] + img[q] for p, q in terms])
 
 
-def chi_poles_host_signed(fracs, beta, vm, tau, wr, eps, ncomp, start=None):
-    """fracs: (comp, peso, Ei, E, z, isign) in queue order, isign 0 (both), +1 or
-    -1.  Returns (iv, tau, w, (sum |terms| of iv, tau, w))."""
-    vm, tau, wr = (np.asarray(x, float) for x in (vm, tau, wr))
-    civ = np.zeros((ncomp, len(vm)), complex) if start is None else np.array(start[0])
-    ctau = np.zeros((ncomp, len(tau))) if start is None else np.array(start[1])
-    cw = np.zeros((ncomp, len(wr)), complex) if start is None else np.array(start[2])
-    mag = [np.abs(civ), np.abs(ctau), np.abs(cw)]
-    tm = beta - tau
-    for comp, peso, ei, E, z, isign in fracs:
-        assert isign in (0, 1, -1)
-        E, z = np.asarray(E, float), np.asarray(z, float)
-        f, s = thermal_host(beta, E - ei)
-        for sg in (0, 1):                      # isign = +1, then -1
-            if isign == (1 if sg else -1):     # a one-sign fraction: the other branch is not its
-                continue
-            for j in range(len(E)):
-                de = E[j] - ei
-                pj = (peso * z[j]) * z[j]
-                t0 = pj * s[j]
-                civ[comp, 0] = civ[comp, 0] + t0
-                mag[0][comp, 0] += abs(t0)
-                tt = pj * np.exp(-(tm if sg else tau) * de)
-                ctau[comp] = ctau[comp] + tt
-                mag[1][comp] += np.abs(tt)
-                num = pj * f[j]
-                if sg:
-                    ci, cr = _cdiv(num, 0.0 + de, vm[1:]), _cdiv(num, wr + de, np.full(len(wr), eps))
-                else:
-                    ci, cr = _cdiv(-num, 0.0 - de, vm[1:]), _cdiv(-num, wr - de, np.full(len(wr), eps))
-                civ[comp, 1:] = civ[comp, 1:] + ci
-                cw[comp] = cw[comp] + cr
-                mag[0][comp, 1:] += np.abs(ci)
-                mag[2][comp] += np.abs(cr)
-    return civ, ctau, cw, tuple(mag)
+chi_poles_host_signed = chi_poles_host      # the isign element is the sixth of a fraction
 
 
 def replay_chi_pair(cfg, states, copt, pair=True, exc=True, record=None):
@@ -131,5 +97,5 @@ def replay_chi_pair(cfg, states, copt, pair=True, exc=True, record=None):
                     fracs.append((comp, _peso_bz(states, k, 1.0, norm2, zeta), states.energies[k], E, z, isign))
     vm, tg = bosonic_matsubara(copt.beta, copt.Lmats), tau_grid(copt.beta, copt.ltau)
     wr = realaxis(copt.wini, copt.wfin, copt.Lreal)
-    iv, tau, w, _ = chi_poles_host_signed(fracs, copt.beta, vm, tg, wr, copt.eps, n_components_ext(cfg, pair, exc))
-    return assemble_ext(cfg, copt, iv, tau, w, spin=False, dens=False, pair=pair, exc=exc)
+    iv, tau, w, _ = chi_poles_host_signed(fracs, copt.beta, vm, tg, wr, copt.eps, n_components(cfg, pair, exc))
+    return assemble(cfg, copt, iv, tau, w, spin=False, dens=False, pair=pair, exc=exc)

@@ -34,7 +34,7 @@ import pytest
 import chi_pair_truth as pt
 import chi_truth as ct
 from chi_pair_host import chi_poles_host_signed, numpy_pair_seeds
-from edgpu import _lib, chi
+from edgpu import _lib, chi, gf
 from edgpu.diag import DiagOptions, ed_diag, post_diag
 from edgpu.hamiltonian import Sector
 from edgpu.params import make_config
@@ -419,7 +419,7 @@ def test_seed_buffer_chunking_gives_the_same_arrays(monkeypatch):
     T, copt, sl = pt.truth("C2"), pt.options("C2"), states("C2")
     rec_w, rec_s = [], []
     whole = chi.build_chi(T.cfg, sl, copt, spin=False, dens=False, pair=True, exc=True, record=rec_w)
-    monkeypatch.setattr(chi, "SEED_BUFFER_BYTES", 1)
+    monkeypatch.setattr(gf, "SEED_BUFFER_BYTES", 1)           # the one knob: gf.seed_fractions reads it
     split = chi.build_chi(T.cfg, sl, copt, spin=False, dens=False, pair=True, exc=True, record=rec_s)
     assert [(r["state"], r["name"], r["isign"], r["norm2"]) for r in rec_w] == \
         [(r["state"], r["name"], r["isign"], r["norm2"]) for r in rec_s]

@@ -126,14 +126,16 @@ def test_finite_temperature_with_twin_vectors():
 
 
 # ------------------------------------------------------------ the kernel alone
-def _seed_batch(src, dst, op, levels, coef, x, nseed=None, nlev=None):
-    """(rc, seeds, norm2) of one ed_sector_seed_batch call; coef: (nseed, nlev) complex."""
+def _seed_batch(src, dst, op, levels, coef, x, nseed=None, nlev=None, out=None):
+    """(rc, seeds, norm2) of one ed_sector_seed_batch call; coef: (nseed, nlev) complex.  out: the device
+    tensor to write into (default: a NaN-filled one, written whole)."""
     import torch
 
     coef = np.ascontiguousarray(coef, dtype=np.complex128)
     nseed = coef.shape[0] if nseed is None else nseed
     lev = np.ascontiguousarray(levels, dtype=np.int32)
-    out = torch.full((max(nseed, 1), dst.dim), float("nan"), dtype=x.dtype, device=x.device)   # written whole
+    if out is None:
+        out = torch.full((max(nseed, 1), dst.dim), float("nan"), dtype=x.dtype, device=x.device)
     n2 = np.full(max(nseed, 1), np.nan)
     st = torch.cuda.current_stream()
     rc = _lib.load().ed_sector_seed_batch(src.handle, dst.handle, op, len(lev) if nlev is None else nlev,
@@ -292,6 +294,61 @@ def test_seed_batch_argument_errors():
         assert _seed_batch(S, D, 1, [0, 0], one, x)[0] == 1                       # repeated level
 
 
+def test_seed_batch_refuses_seeds_overlapping_the_vector():
+    """Norb = 1, Nbath = 1, (1, 1) -> (2, 1), one seed: the gather reads the vector while other threads store
+    output rows, so an output that shares one element with it is refused before any launch."""
+    import torch
+
+    cfg = make_config(Norb=1, Nbath=1)
+    with Sector(cfg, 1, 1, stored=False, direct=True, real=True) as S, \
+            Sector(cfg, 2, 1, stored=False, direct=True, real=True) as D:
+        ds, dd = S.dim, D.dim
+        assert (ds, dd) == (4, 2)
+        xh = _random(ds, False, 1)
+        levels, coef = [0, 1], np.ones((1, 2))
+        rc, ref, ref2 = _seed_batch(S, D, 1, levels, coef, torch.from_numpy(xh).cuda())
+        assert rc == 0 and not np.any(np.isnan(ref)) and ref2[0] > 0
+        # the vector's last element is the first of the output
+        buf = torch.full((ds + dd,), float("nan"), dtype=torch.float64, device="cuda")
+        buf[:ds] = torch.from_numpy(xh)
+        rc, after, n2 = _seed_batch(S, D, 1, levels, coef, buf[:ds], out=buf[ds - 1:ds - 1 + dd])
+        assert rc == 1 and after[0] == xh[-1] and np.all(np.isnan(after[1:])) and np.all(np.isnan(n2))
+        # the output's last element is the first of the vector
+        buf2 = torch.full((dd - 1 + ds,), float("nan"), dtype=torch.float64, device="cuda")
+        buf2[dd - 1:] = torch.from_numpy(xh)
+        rc, after, n2 = _seed_batch(S, D, 1, levels, coef, buf2[dd - 1:], out=buf2[:dd])
+        assert rc == 1 and after[-1] == xh[0] and np.all(np.isnan(after[:-1])) and np.all(np.isnan(n2))
+        assert np.array_equal(buf[:ds].cpu().numpy(), xh) and np.array_equal(buf2[dd - 1:].cpu().numpy(), xh)
+        # the output right behind the vector is accepted
+        rc, after, n2 = _seed_batch(S, D, 1, levels, coef, buf[:ds], out=buf[ds:])
+        assert rc == 0 and np.array_equal(after, ref[0]) and np.array_equal(n2, ref2)
+
+
+def test_sector_method_and_out_argument():
+    import torch
+
+    cfg = make_config(Norb=2, Nbath=5, Nspin=1, bath_type="hybrid", bath="random", seed=3)
+    with Sector(cfg, 3, 3, stored=False, direct=True, real=True) as S, \
+            Sector(cfg, 4, 3, stored=False, direct=True, real=True) as D:
+        xh, coef = _random(S.dim, False, 4), _coefs9(False)
+        rc, ref, ref2 = _seed_batch(S, D, 1, [0, 1, 2], coef, torch.from_numpy(xh).cuda())
+        assert rc == 0
+        seeds, n2 = S.seed_batch(xh, D, 1, [0, 1, 2], coef)
+        assert seeds.shape == (9, D.dim) and seeds.is_cuda and seeds.dtype == torch.float64 and n2.shape == (9,)
+        assert np.array_equal(seeds.cpu().numpy(), ref) and np.array_equal(n2, ref2)      # the raw call's bits
+        out = torch.full((9, D.dim), float("nan"), dtype=torch.float64, device="cuda")
+        seeds2, n22 = S.seed_batch(torch.from_numpy(xh).cuda(), D, 1, [0, 1, 2], coef, out=out)
+        assert seeds2 is out and torch.equal(seeds, out) and np.array_equal(n2, n22)
+        rows = torch.full((12, D.dim), float("nan"), dtype=torch.float64, device="cuda")
+        S.seed_batch(xh, D, 1, [0, 1, 2], coef, out=rows[2:11])                           # rows of a larger tensor
+        assert torch.equal(rows[2:11], seeds) and bool(torch.isnan(rows[:2]).all()) and bool(torch.isnan(rows[11:]).all())
+        for bad in (torch.empty((8, D.dim), dtype=torch.float64, device="cuda"),             # shape
+                    torch.empty((9, D.dim), dtype=torch.complex128, device="cuda"),          # dtype
+                    torch.empty((D.dim, 9), dtype=torch.float64, device="cuda").T):          # not contiguous
+            with pytest.raises(ValueError):
+                S.seed_batch(xh, D, 1, [0, 1, 2], coef, out=bad)
+
+
 # ------------------------------------------------------------ fused seeds in build_gf
 @pytest.mark.parametrize("name", ["H3", "nonsu2"])
 def test_fused_seeds_match_the_unfused_path(name):
@@ -313,3 +370,22 @@ def test_fused_seeds_match_the_unfused_path(name):
     assert [(a["channel"], a["isector"], a["op"], a["nlanc"]) for a in r0] == \
         [(b["channel"], b["isector"], b["op"], b["nlanc"]) for b in r1]
     assert dm < 1e-12 and dr < 1e-8
+
+
+def test_seed_buffer_chunking_gives_the_same_arrays(monkeypatch):
+    """SEED_BUFFER_BYTES below one seed: gf.seed_fractions builds and tridiagonalises the fused seeds of H3
+    one row at a time."""
+    from edgpu import gf as gfmod
+
+    cfg, sl = ot.truth("H3").cfg, states("H3")
+    rec_w, rec_s = [], []
+    whole = build_gf(cfg, sl, gopt("H3", fused_seeds=True), record=rec_w)
+    monkeypatch.setattr(gfmod, "SEED_BUFFER_BYTES", 1)
+    split = build_gf(cfg, sl, gopt("H3", fused_seeds=True), record=rec_s)
+    assert len(rec_w) == len(rec_s) > 0
+    assert [(r["channel"], r["isector"], r["op"], r["norm2"]) for r in rec_w] == \
+        [(r["channel"], r["isector"], r["op"], r["norm2"]) for r in rec_s]
+    for a, b in zip(whole, split):
+        print(f"whole against split: {np.max(np.abs(a - b)) / np.max(np.abs(a)):.1e}")
+    for a, b in zip(whole, split):
+        assert np.any(a != 0) and np.array_equal(a, b)

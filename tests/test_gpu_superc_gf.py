@@ -113,15 +113,16 @@ def test_host_paths_bit_identical_and_fused_seeds():
 
 
 # ------------------------------------------------------------ the kernel alone
-def _seed_plan(src, dst, levels, ops, terms, x, nlev=None, nseed=None, vtype=None):
-    """(rc, seeds, norm2) of one ed_sector_seed_plan call; the output starts as NaN."""
+def _seed_plan(src, dst, levels, ops, terms, x, nlev=None, nseed=None, vtype=None, out=None):
+    """(rc, seeds, norm2) of one ed_sector_seed_plan call; the output (`out`, or a tensor of its own) starts as NaN."""
     import torch
 
     lev = np.ascontiguousarray(levels, dtype=np.int32)
     op = np.ascontiguousarray(ops, dtype=np.int32)
     tt = np.ascontiguousarray(terms, dtype=np.int32).reshape(-1, 2)
     ns = len(tt) if nseed is None else nseed
-    out = torch.full((max(len(tt), 1), dst.dim), float("nan"), dtype=x.dtype, device=x.device)    # written whole
+    if out is None:
+        out = torch.full((max(len(tt), 1), dst.dim), float("nan"), dtype=x.dtype, device=x.device)    # written whole
     n2 = np.full(max(len(tt), 1), np.nan)
     stream = torch.cuda.current_stream()
     rc = _lib.load().ed_sector_seed_plan(src.handle, dst.handle, len(lev) if nlev is None else nlev,
@@ -299,3 +300,76 @@ def test_seed_plan_refusals_leave_the_output_untouched():
         rc, _, _ = _seed_plan(S, D, [0, 1, 2, Ns, Ns + 1, Ns + 2], [1, 1, 1, 0, 0, 0], [(0, 5), (2, 3)], x)
         assert rc == 0
 
+
+def test_seed_plan_refuses_seeds_overlapping_the_vector():
+    """S2, sz 0 -> +1, one seed: an output that shares one element with the vector is refused before any
+    launch (the gather reads the vector while other threads store output rows)."""
+    import torch
+
+    cfg = st.config("S2")
+    levels, ops, terms = [0, cfg.Ns], [1, 0], [(0, 1)]
+    with Sector(cfg, 0, 0, stored=False, direct=True, real=True) as S, \
+            Sector(cfg, 1, 0, stored=False, direct=True, real=True) as D:
+        ds, dd = S.dim, D.dim
+        xh = _random(ds, False, 1)
+        rc, ref, ref2 = _seed_plan(S, D, levels, ops, terms, torch.from_numpy(xh).cuda())
+        assert rc == 0 and not np.any(np.isnan(ref)) and ref2[0] > 0
+        # the vector's last element is the first of the output
+        buf = torch.full((ds + dd,), float("nan"), dtype=torch.float64, device="cuda")
+        buf[:ds] = torch.from_numpy(xh)
+        rc, after, n2 = _seed_plan(S, D, levels, ops, terms, buf[:ds], out=buf[ds - 1:ds - 1 + dd])
+        assert rc == 1 and after[0] == xh[-1] and np.all(np.isnan(after[1:])) and np.all(np.isnan(n2))
+        # the output's last element is the first of the vector
+        buf2 = torch.full((dd - 1 + ds,), float("nan"), dtype=torch.float64, device="cuda")
+        buf2[dd - 1:] = torch.from_numpy(xh)
+        rc, after, n2 = _seed_plan(S, D, levels, ops, terms, buf2[dd - 1:], out=buf2[:dd])
+        assert rc == 1 and after[-1] == xh[0] and np.all(np.isnan(after[:-1])) and np.all(np.isnan(n2))
+        assert np.array_equal(buf[:ds].cpu().numpy(), xh) and np.array_equal(buf2[dd - 1:].cpu().numpy(), xh)
+        # the output right behind the vector is accepted
+        rc, after, n2 = _seed_plan(S, D, levels, ops, terms, buf[:ds], out=buf[ds:])
+        assert rc == 0 and np.array_equal(after, ref[0]) and np.array_equal(n2, ref2)
+
+
+def test_sector_method_and_out_argument():
+    import torch
+
+    cfg = st.config("S2")
+    levels, ops, terms = _plan_for(cfg, +1)
+    ns = len(terms)
+    with Sector(cfg, 0, 0, stored=False, direct=True, real=True) as S, \
+            Sector(cfg, 1, 0, stored=False, direct=True, real=True) as D:
+        xh = _random(S.dim, False, 4)
+        rc, ref, ref2 = _seed_plan(S, D, levels, ops, terms, torch.from_numpy(xh).cuda())
+        assert rc == 0
+        seeds, n2 = S.seed_plan(xh, D, levels, ops, terms)
+        assert seeds.shape == (ns, D.dim) and seeds.is_cuda and seeds.dtype == torch.float64 and n2.shape == (ns,)
+        assert np.array_equal(seeds.cpu().numpy(), ref) and np.array_equal(n2, ref2)      # the raw call's bits
+        out = torch.full((ns, D.dim), float("nan"), dtype=torch.float64, device="cuda")
+        seeds2, n22 = S.seed_plan(torch.from_numpy(xh).cuda(), D, levels, ops, terms, out=out)
+        assert seeds2 is out and torch.equal(seeds, out) and np.array_equal(n2, n22)
+        for bad in (torch.empty((ns + 1, D.dim), dtype=torch.float64, device="cuda"),        # shape
+                    torch.empty((ns, D.dim), dtype=torch.complex128, device="cuda"),         # dtype
+                    torch.empty((D.dim, ns), dtype=torch.float64, device="cuda").T):         # not contiguous
+            with pytest.raises(ValueError):
+                S.seed_plan(xh, D, levels, ops, terms, out=bad)
+        with pytest.raises(ValueError):
+            S.seed_plan(xh, D, levels, ops[:-1], terms)                                      # one op per level
+
+
+def test_seed_buffer_chunking_gives_the_same_arrays(monkeypatch):
+    """SEED_BUFFER_BYTES below one seed: gf.seed_fractions builds and tridiagonalises the fused seeds of S2
+    one row at a time."""
+    from edgpu import gf as gfmod
+
+    cfg, sl = st.truth("S2").cfg, states("S2")
+    rec_w, rec_s = [], []
+    whole = build_gf_superc(cfg, sl, gopt("S2", fused_seeds=True), record=rec_w)
+    monkeypatch.setattr(gfmod, "SEED_BUFFER_BYTES", 1)
+    split = build_gf_superc(cfg, sl, gopt("S2", fused_seeds=True), record=rec_s)
+    assert len(rec_w) == len(rec_s) > 0
+    assert [(r["channel"], r["isector"], r["op"], r["norm2"]) for r in rec_w] == \
+        [(r["channel"], r["isector"], r["op"], r["norm2"]) for r in rec_s]
+    for a, b in zip(whole, split):
+        print(f"whole against split: {np.max(np.abs(a - b)) / np.max(np.abs(a)):.1e}")
+    for a, b in zip(whole, split):
+        assert np.any(a != 0) and np.array_equal(a, b)

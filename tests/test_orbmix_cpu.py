@@ -97,6 +97,18 @@ def test_job_list_orders_mixed_jobs_after_the_diagonal():
     assert at == len(jobs) and at - nd == 6 * 4 * sl.size    # (1,3): all four targets exist
 
 
+def test_jobs_have_names_and_still_unpack():
+    """`_job_list(...)[0][0]`: six fields by position and by name, the seed five."""
+    jobs, _ = _job_list(ot.config("H3"), run("H3")["sl"])
+    job = jobs[0]
+    comp, tag, k, seed, src, dst = job
+    assert len(job) == 6 and (job.comp, job.tag, job.k, job.seed, job.src, job.dst) == (comp, tag, k, seed, src, dst)
+    assert job.seed.terms is job[3][3] and job.dst is job[5] and job.src is job[4]
+    op, isign, ispin, terms, weight = seed
+    assert (seed.op, seed.isign, seed.ispin, seed.terms, seed.weight) == (op, isign, ispin, terms, weight)
+    assert seed == (1, +1, 0, [(0, 1)], 1.0) and job[:3] == ((0, 0, 0, 0), ("diag", 0, 0), 0)
+
+
 @pytest.mark.parametrize("name", MODELS)
 def test_offdiagonal_g_matches_the_dense_lehmann_sum(name):
     T, r = ot.truth(name), run(name)
