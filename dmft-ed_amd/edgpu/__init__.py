@@ -16,6 +16,8 @@ Modules:
               seeds (Sector.seed_diag), Lanczos, bosonic / tau / real-axis poles;
               pair and inter-orbital parts from two-operator seeds
               (Sector.seed_pair)
+  sigma       self-energy, Weiss field and bath hybridisation from G (and F):
+              ed_sigma_build, one work item per (block, grid point)
   observables impurity observables and local energies of the kept states
               (observables_impurity / local_energy_impurity) from device
               vectors: Sector.nn_moments / Sector.expect
@@ -27,6 +29,7 @@ first use and its absence is an error (no CPU fallback).
 from .params import EDConfig, make_config, init_dmft_bath, random_bath  # noqa: F401
 from .sectors import setup_pointers  # noqa: F401
 from .chi import Chi, ChiOptions, build_chi  # noqa: F401
+from .sigma import Sigma, bath_functions, build_sigma  # noqa: F401
 
 __all__ = ["EDConfig", "make_config", "init_dmft_bath", "random_bath", "setup_pointers", "Chi", "ChiOptions",
-           "build_chi"]
+           "build_chi", "Sigma", "build_sigma", "bath_functions"]

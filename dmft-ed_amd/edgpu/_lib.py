@@ -75,6 +75,9 @@ SIGNATURES = {
                          ctypes.c_int),
     "ed_chi_add_poles_signed": ([_i32, _P, _P, _P, _P, _P, _P, _P, _f64, _P, _i32, _P, _i32, _P, _i32, _f64, _P, _P,
                                  _P, _P], ctypes.c_int),
+    "ed_sigma_blocks": ([_P, _P, _P], ctypes.c_int),
+    "ed_sigma_build_blocks": ([_i32, _P, _i32, _i32, _f64, _i32, _f64, _f64, _i32, _f64] + [_P] * 15, ctypes.c_int),
+    "ed_sigma_build": ([_P, _f64, _i32, _f64, _f64, _i32, _f64] + [_P] * 15, ctypes.c_int),
     "ed_gpu_init": ([_P], ctypes.c_int),
     "ed_gpu_set_device": ([_i32], ctypes.c_int),
     "ed_gpu_build_sector": ([_i32, _i32, _i32, _P], ctypes.c_int),

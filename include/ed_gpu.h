@@ -544,6 +544,56 @@ int ed_chi_add_poles_signed(int32_t nfrac, const int32_t* npole, const double* E
                             const double* wr, int32_t lreal, double eps, double* chi_iv, double* chi_tau,
                             double* chi_w, void* stream);
 
+/* ------------------------------------------- self-energy and Weiss field
+ * The second half of buildGF_impurity (ED_GREENS_FUNCTIONS.f90:22-63):
+ * build_sigma_normal (ED_GF_NORMAL.f90:656-731), build_sigma_superc
+ * (ED_GF_SUPERC.f90:826-929) and build_sigma_nonsu2 (from ED_GF_NONSU2.f90:977),
+ * block by block.  One block: n impurity indices
+ * idx[i] = ispin*norb + iorb, its one-body matrix h = impHloc - mu, and the
+ * bath as np poles,
+ *   Delta_ij(z) = sum_p c_p w[p][i] conj(w[p][j]) / (z - e[p]),
+ *   invG0 = z - h - Delta,  G0 = invG0^-1,  Sigma = invG0 - G^-1.
+ * nambu = 1: n = 2, idx[0] = idx[1] = iorb, the indices are (c_up, c+_dw) of
+ * that orbital and G is read as [[G, F], [F, -conj(G)]], the last entry at the
+ * mirrored index of a symmetric real grid. */
+#define ED_SIGMA_MAX_N     6
+#define ED_SIGMA_MAX_POLES 64
+typedef struct ed_sigma_block {
+  int32_t n, np, nambu, pad_;
+  int32_t idx[ED_SIGMA_MAX_N];
+  int32_t pad2_[2];
+  double h[ED_SIGMA_MAX_N][ED_SIGMA_MAX_N][2];
+  double e[ED_SIGMA_MAX_POLES];
+  double c[ED_SIGMA_MAX_POLES][2];
+  double w[ED_SIGMA_MAX_POLES][ED_SIGMA_MAX_N][2];
+} ed_sigma_block;
+/* The blocks and pole tables of p (host only, nothing is launched):
+ * blocks[nspin*norb] at most, *nblk of them written.  ED_ERR_UNSUPPORTED for
+ * superc with a hybrid or replica bath, whose orbital off-diagonal G and F are
+ * not built. */
+int ed_sigma_blocks(const ed_params* p, ed_sigma_block* blocks, int32_t* nblk);
+/* Sigma, G0 and Delta of nblk blocks on the grids i w_n = i pi/beta (2n - 1),
+ * n = 1..lmats, and w + i eps on the lreal points from wini to wfin, one work
+ * item per (block, grid point) and one launch per distinct n.  gm, gr (and fm,
+ * fr for Nambu blocks): complex(8) device arrays (nspin, nspin, norb, norb, L)
+ * as build_gf leaves them; both NULL: only G0 and Delta are computed and
+ * smats ... sareal are not touched.  Outputs: device arrays of the same
+ * layout, zero outside the blocks; samats, sareal, f0mats, f0real only with
+ * Nambu blocks.  ED_ERR_ARG, before anything is launched: n outside {1, 2, 3,
+ * 4, 6}, np outside 1..64, two blocks sharing an index, a Nambu block on a
+ * real grid with wini != -wfin, an output sharing a byte with an input or
+ * another output.  Asynchronous on `stream`: no host synchronisation. */
+int ed_sigma_build_blocks(int32_t nblk, const ed_sigma_block* blocks, int32_t nspin, int32_t norb, double beta,
+                          int32_t lmats, double wini, double wfin, int32_t lreal, double eps, const double* gm,
+                          const double* gr, const double* fm, const double* fr, double* smats, double* sreal,
+                          double* g0mats, double* g0real, double* dmats, double* dreal, double* samats,
+                          double* sareal, double* f0mats, double* f0real, void* stream);
+/* The same with the blocks of ed_sigma_blocks(p). */
+int ed_sigma_build(const ed_params* p, double beta, int32_t lmats, double wini, double wfin, int32_t lreal,
+                   double eps, const double* gm, const double* gr, const double* fm, const double* fr, double* smats,
+                   double* sreal, double* g0mats, double* g0real, double* dmats, double* dreal, double* samats,
+                   double* sareal, double* f0mats, double* f0real, void* stream);
+
 /* ------------------------------------------------------ reference-style API */
 int ed_gpu_init(const ed_params* p);          /* ed_init_solver parameter hand-over */
 int ed_gpu_set_device(int32_t device);
