@@ -21,10 +21,8 @@
 //                 ED_GF_CHIDENS.f90:523-586 and :596-659; DESIGN.md section
 //                 13): the gather form of k_seed_plan with seed_image2
 //                 (ed_seed_pair.hpp) in place of seed_image.
-//   k_chi_poles   the pole sums of add_to_lanczos_spinChi
-//                 (ED_GF_CHISPIN.f90:254-323) on the bosonic Matsubara, the
-//                 imaginary-time and the real-frequency grids, with both
-//                 isign branches of a fraction or one of them.
+// (k_chi_poles, the pole sums of add_to_lanczos_spinChi, is in ed_poles.hip,
+// the unit that launches it.)
 #pragma once
 #include "ed_chi_host.hpp"
 #include "ed_seed.hpp"  // seed_abs2, k_seed_scale
@@ -117,83 +115,6 @@ __global__ void __launch_bounds__(kBlock) k_seed_pair(const uint32_t* __restrict
 #pragma unroll
   for (int s = 0; s < kPairMaxSeeds; s++)
     if (s < P.nseed) block_partial(n2[s], partials + (size_t)s * gridDim.x);
-}
-
-// ------------------------------------------------ susceptibility pole sums
-// add_to_lanczos_spinChi (ED_GF_CHISPIN.f90:254-323) for one tridiagonalisation,
-// called with isign = +1 and then -1 as the reference's builders do
-// (ED_GF_CHISPIN.f90:126-131).  With D = E_j - Ei, peso_j = (peso * z_j) * z_j,
-// f_j = 1 - exp(-beta D) and s_j = f_j / D (chi_thermal, staged by the host),
-// a fraction adds pole by pole
-//   isign +1: iv(0) += peso_j s_j      iv(i) += -peso_j f_j / (i v_i - D)
-//             tau(i) += peso_j exp(-tau_i D)
-//             w(i)   += -peso_j f_j / (wr_i + i eps - D)
-//   isign -1: iv(0) += peso_j s_j      iv(i) += peso_j f_j / (i v_i + D)
-//             tau(i) += peso_j exp(-(beta - tau_i) D)
-//             w(i)   += peso_j f_j / (wr_i + i eps + D)
-// all poles with +1 first, then all with -1.  ChiFrac::sel picks the branches:
-// kChiBoth (a Hermitian seed: the two calls above), kChiPlus or kChiMinus (one
-// call with that isign: a seed O^+|n> or O|n> of a non-Hermitian O, DESIGN.md
-// section 13).  One thread per grid point, the
-// three grids laid end to end: iv 0..lmats, tau 0..ltau, w 1..lreal; fraction
-// and pole data are wave-uniform; the arrays stay in HBM across flushes.
-struct ChiFrac {
-  int32_t p0, np, comp, sel;  // sel: kChiBoth / kChiPlus / kChiMinus (ed_chi_host.hpp)
-  double peso, ei;  // w_n * norm2 (real), Ei
-};
-
-static __global__ void __launch_bounds__(kBlock) k_chi_poles(const ChiFrac* __restrict__ fr, int nfrac,
-                                                      const double* __restrict__ E, const double* __restrict__ z,
-                                                      const double* __restrict__ fth, const double* __restrict__ sth,
-                                                      double beta, const double* __restrict__ vm, int nmats,
-                                                      const double* __restrict__ tau, int ntau,
-                                                      const double* __restrict__ wr, int lreal, double eps,
-                                                      double2* __restrict__ civ, double* __restrict__ ctau,
-                                                      double2* __restrict__ cw) {
-  const int t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= nmats + ntau + lreal) return;
-  // kind 0: iv(0), 1: iv(i >= 1), 2: tau, 3: real axis
-  const int kind = t == 0 ? 0 : t < nmats ? 1 : t < nmats + ntau ? 2 : 3;
-  const int i = kind < 2 ? t : kind == 2 ? t - nmats : t - nmats - ntau;
-  const int L = kind < 2 ? nmats : kind == 2 ? ntau : lreal;
-  const double re_w = kind == 3 ? wr[i] : 0.0;  // dcmplx(0, vm(i)); dcmplx(wr(i), eps)
-  const double im_w = kind == 1 ? vm[i] : eps;
-  const double tp = kind == 2 ? tau[i] : 0.0, tm = beta - tp;
-  int cur = -1;
-  double2 g = make_double2(0.0, 0.0);
-  for (int f = 0; f < nfrac; f++) {
-    const ChiFrac q = fr[f];
-    if (q.comp != cur) {
-      if (cur >= 0) {
-        if (kind == 2) ctau[(int64_t)cur * L + i] = g.x;
-        else (kind == 3 ? cw : civ)[(int64_t)cur * L + i] = g;
-      }
-      cur = q.comp;
-      g = kind == 2 ? make_double2(ctau[(int64_t)cur * L + i], 0.0) : (kind == 3 ? cw : civ)[(int64_t)cur * L + i];
-    }
-    for (int sg = 0; sg < 2; sg++) {  // isign = +1, then -1
-      if (q.sel == (sg ? kChiPlus : kChiMinus)) continue;  // a one-sign fraction: the other branch is not its
-      for (int j = 0; j < q.np; j++) {
-        const double zj = z[q.p0 + j];
-        const double de = E[q.p0 + j] - q.ei;
-        const double peso = (q.peso * zj) * zj;
-        if (kind == 0) {
-          g.x = g.x + peso * sth[q.p0 + j];
-        } else if (kind == 2) {
-          g.x = g.x + peso * exp(-(sg ? tm : tp) * de);
-        } else {
-          const double num = peso * fth[q.p0 + j];
-          const double2 c = sg ? cdiv(make_double2(num, 0.0), re_w + de, im_w)
-                               : cdiv(make_double2(-num, 0.0), re_w - de, im_w);
-          g = make_double2(g.x + c.x, g.y + c.y);
-        }
-      }
-    }
-  }
-  if (cur >= 0) {
-    if (kind == 2) ctau[(int64_t)cur * L + i] = g.x;
-    else (kind == 3 ? cw : civ)[(int64_t)cur * L + i] = g;
-  }
 }
 
 }  // namespace edg

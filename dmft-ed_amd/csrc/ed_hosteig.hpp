@@ -366,7 +366,7 @@ inline void trl_arrowhead(double* Tm, int ma, int nkeep, double beta, const doub
   }
 }
 
-// ------------------- degeneracy screen (described above probe_screen, ed_lib.hip)
+// ------------------- degeneracy screen (described above probe_screen, ed_eigh.hip)
 constexpr int kScreenChunk = 10;  // steps between two decisions
 constexpr int kScreenMaxSteps = 400;
 // a copy missed within the margin below ev[nev-1] stays missed, so the

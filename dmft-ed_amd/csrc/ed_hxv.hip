@@ -11,6 +11,31 @@
 
 using namespace edg;
 
+namespace edg {
+// -------------------------------- row split: columns the held rows gather
+// One bit per sector column, set for every column an off-diagonal element of
+// rows [row0, row0 + n) refers to (gen_row's elements: stored and matrix-free
+// alike).  The halo of a rank's row block for the split H·v (edgpu.dist).
+struct MarkAcc {
+  DevIndex idx;
+  uint32_t* mask;
+  __device__ __forceinline__ void diag(double, double) {}
+  __device__ __forceinline__ void off(uint32_t k, double, double) {
+    const uint32_t c = (uint32_t)idx(k);
+    atomicOr(mask + (c >> 5), 1u << (c & 31));
+  }
+};
+static __global__ void __launch_bounds__(kBlock) k_mark_cols(const EdModel* __restrict__ Mp,
+                                                      const uint32_t* __restrict__ map, int64_t n,
+                                                      DevIndex idx, uint32_t* mask) {
+  const EdModel& M = *Mp;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    MarkAcc a{idx, mask};
+    gen_row(M, map[i], a);
+  }
+}
+}  // namespace edg
+
 template <bool HC, bool VC, bool PL, class Epi>
 static int launch_direct(ed_sector* s, const void* x, Epi epi, hipStream_t st) {
   using V = val_t<VC>;

@@ -3,8 +3,9 @@
 // Kernels (one thread per basis row, 256-thread blocks = 4 wavefronts,
 // grid-strided over whole 64-row slices so that a wavefront is exactly one
 // SELL slice):
-//   k_build_map    H%map from the (off, rank) tables        build_sector ED_SETUP.f90:886-984
-//   k_count        elements per row + SELL-64 slice width   ed_buildH_c pass 1
+//   (k_build_map, k_count and the other non-template build kernels are in
+//   ed_build_kernels.hpp; each non-template kernel is defined where only the
+//   unit that launches it includes it)
 //   k_fill         SELL-64 fill, reference row order        ed_buildH_c + sp_insert_element
 //   k_spmv         stored H·v, SELL-64                      spMatVec_cc STORED_HxV.f90:132-143
 //   k_spmv_pk      same, 32-bit {col|dictionary index} words (real H)
@@ -171,100 +172,7 @@ struct DevIndex {
   }
 };
 
-// ------------------------------------------------------------- basis / map
-static __global__ void __launch_bounds__(kBlock) k_build_map(const int64_t* __restrict__ blk_off,
-                                                      const uint32_t* __restrict__ blk_idw, int nblk,
-                                                      const int32_t* __restrict__ need_cls,
-                                                      const uint32_t* __restrict__ by_cls,
-                                                      const int32_t* __restrict__ cls_start, int ns,
-                                                      int64_t dim, uint32_t* __restrict__ map) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < dim;
-       i += (int64_t)gridDim.x * kBlock) {
-    int lo = 0, hi = nblk;  // blk_off[lo] <= i < blk_off[hi]
-    while (hi - lo > 1) {
-      int mid = (lo + hi) >> 1;
-      if (blk_off[mid] <= i) lo = mid;
-      else hi = mid;
-    }
-    uint32_t idw = blk_idw[lo];
-    uint32_t iup = by_cls[cls_start[need_cls[idw]] + (i - blk_off[lo])];
-    map[i] = iup | (idw << ns);
-  }
-}
-
 // ------------------------------------------------------------ stored build
-struct CountAcc {
-  int n = 0;
-  __device__ __forceinline__ void diag(double, double) {}
-  __device__ __forceinline__ void off(uint32_t, double, double) { n++; }
-};
-
-// cnt[i] = off-diagonal elements of row i; width[s] = max over slice s.
-static __global__ void __launch_bounds__(kBlock) k_count(const EdModel* __restrict__ Mp,
-                                                  const uint32_t* __restrict__ map, int64_t dim,
-                                                  int64_t nslice, uint16_t* __restrict__ cnt,
-                                                  int32_t* __restrict__ width) {
-  const EdModel& M = *Mp;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nslice * 64;
-       i += (int64_t)gridDim.x * kBlock) {
-    int c = 0;
-    if (i < dim) {
-      CountAcc a;
-      gen_row(M, map[i], a);
-      c = a.n;
-      cnt[i] = (uint16_t)c;
-    }
-    int w = wave_max(c);
-    if ((threadIdx.x & 63) == 0) width[i >> 6] = w;
-  }
-}
-
-// Exclusive scan of 64*width -> sptr (int64), three-pass.
-// *out += sum of n 16-bit counts (grid-strided; wave sums, one atomic per wave)
-static __global__ void __launch_bounds__(kBlock) k_sum_u16(const uint16_t* __restrict__ c, int64_t n,
-                                                    unsigned long long* out) {
-  unsigned long long acc = 0;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) acc += c[i];
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out, acc);
-}
-
-static __global__ void __launch_bounds__(1024) k_scan_blocks(const int32_t* __restrict__ width, int64_t n,
-                                                      int64_t* __restrict__ out,
-                                                      int64_t* __restrict__ bsum) {
-  __shared__ int64_t s[1024];
-  int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-  int64_t x = (i < n) ? 64 * (int64_t)width[i] : 0;
-  s[threadIdx.x] = x;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    int64_t t = (threadIdx.x >= (unsigned)o) ? s[threadIdx.x - o] : 0;
-    __syncthreads();
-    s[threadIdx.x] += t;
-    __syncthreads();
-  }
-  if (i < n) out[i] = s[threadIdx.x] - x;  // exclusive within block
-  if (threadIdx.x == 1023) bsum[blockIdx.x] = s[1023];
-}
-static __global__ void k_scan_spine(int64_t* __restrict__ bsum, int64_t nb, int64_t* __restrict__ total) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    int64_t acc = 0;
-    for (int64_t b = 0; b < nb; b++) {
-      int64_t t = bsum[b];
-      bsum[b] = acc;
-      acc += t;
-    }
-    *total = acc;
-  }
-}
-static __global__ void __launch_bounds__(1024) k_scan_add(int64_t* __restrict__ out, int64_t n,
-                                                   const int64_t* __restrict__ bsum,
-                                                   const int64_t* __restrict__ total) {
-  int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-  if (i < n) out[i] += bsum[blockIdx.x];
-  if (i == 0) out[n] = *total;
-}
-
 template <bool HC>
 struct FillAcc {
   using H = val_t<HC>;
@@ -348,7 +256,7 @@ struct EpiStore {
   __device__ __forceinline__ void finish(double) {}
 };
 
-// Thick-restart Lanczos step j past a restart (Trlan::step, ed_lib.hip):
+// Thick-restart Lanczos step j past a restart (Trlan::step, ed_eigh.hip):
 // the three-term part of the recurrence is applied as H v_j is stored, with
 // the spectral shift sigma = alpha_{j-1},
 //   w = (H - sigma) v_j - beta_{j-1} v_{j-1}
@@ -454,16 +362,6 @@ __device__ __forceinline__ double2 ld_wt(const double2* p) {
                       __hip_atomic_load((const double*)p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-// Two-pass finishing kernels of one Lanczos step (one block of kBlock threads).
-static __global__ void __launch_bounds__(kBlock) k_lanc_fin_a(const double* __restrict__ partials, int n,
-                                                       LancState* st, double* alpha_out) {
-  if (st->done) return;
-  const double tot = sum_partials(partials, n);
-  if (threadIdx.x == 0) {
-    st->alpha = tot;
-    alpha_out[st->iter] = tot;
-  }
-}
 __device__ __forceinline__ void lanc_set_beta(double tot, LancState* st, double* beta_out) {
   const double b = sqrt(tot);
   const int it = st->iter;
@@ -472,12 +370,6 @@ __device__ __forceinline__ void lanc_set_beta(double tot, LancState* st, double*
   st->invb = 1.0 / b;
   st->iter = it + 1;
   if (b < st->thresh) st->done = 1;
-}
-static __global__ void __launch_bounds__(kBlock) k_lanc_fin_b(const double* __restrict__ partials, int n,
-                                                       LancState* st, double* beta_out) {
-  if (st->done) return;
-  const double tot = sum_partials(partials, n);
-  if (threadIdx.x == 0) lanc_set_beta(tot, st, beta_out);
 }
 
 // ------------------------------------------------------------- stored H·v
@@ -572,134 +464,6 @@ __device__ __forceinline__ uint32_t dict_hash(unsigned long long k) {
   k *= 0xff51afd7ed558ccdull;
   k ^= k >> 33;
   return (uint32_t)k & (kDictTable - 1);
-}
-
-// Insert every value's bit pattern; plain reads first so that the few
-// distinct keys cost one CAS each, not one per slot.
-// Wave-level deduplication before the table: the lanes of a wavefront read 64
-// consecutive SELL slots, which hold only a few distinct values (hoppings);
-// one leader per distinct key goes to the table.  Without it every slot did a
-// read (and the first ones a CAS) of the same few table lines: all of the
-// device's requests on one L2 channel (N28: 1.05 ms; c4 farm: 0.75 ms per
-// sector, 0.125 s of the serial configs[3] farm).
-__device__ __forceinline__ bool wave_key_leader(unsigned long long key) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long pending = __ballot(1);
-  bool lead = false;
-  while (pending) {
-    const int l = __ffsll((long long)pending) - 1;
-    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)key, l);
-    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), l);
-    const unsigned long long kl = ((unsigned long long)hi << 32) | lo;
-    const unsigned long long same = __ballot(key == kl);
-    lead |= lane == l;
-    pending &= ~same;
-  }
-  return lead;
-}
-
-static __global__ void __launch_bounds__(kBlock) k_dict_insert(const double* __restrict__ vals, int64_t n,
-                                                        unsigned long long* table,
-                                                        unsigned int* overflow) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const unsigned long long key = (unsigned long long)__double_as_longlong(vals[i]);
-    if (!wave_key_leader(key)) continue;
-    if (key == kDictEmpty) {
-      atomicOr(overflow, 1u);
-      continue;
-    }
-    uint32_t h = dict_hash(key);
-    bool done = false;
-    for (int probe = 0; probe < kDictTable && !done; probe++) {
-      const unsigned long long cur = ((volatile unsigned long long*)table)[h];
-      if (cur == key) {
-        done = true;
-      } else if (cur == kDictEmpty) {
-        const unsigned long long prev = atomicCAS(table + h, kDictEmpty, key);
-        if (prev == kDictEmpty || prev == key) done = true;
-        else h = (h + 1) & (kDictTable - 1);  // lost the race to another key: probe on
-      } else {
-        h = (h + 1) & (kDictTable - 1);
-      }
-    }
-    if (!done) atomicOr(overflow, 1u);
-  }
-}
-
-static __global__ void __launch_bounds__(kBlock) k_dict_pack(const int32_t* __restrict__ cols,
-                                                      const double* __restrict__ vals, int64_t n,
-                                                      const unsigned long long* __restrict__ table,
-                                                      const uint8_t* __restrict__ tidx,
-                                                      uint32_t* __restrict__ words) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const unsigned long long key = (unsigned long long)__double_as_longlong(vals[i]);
-    uint32_t h = dict_hash(key);
-    while (table[h] != key) h = (h + 1) & (kDictTable - 1);  // present by construction
-    words[i] = (uint32_t)cols[i] | ((uint32_t)tidx[h] << kPackShift);
-  }
-}
-
-// Complex H (the reference's complex(8) arithmetic, ED_SPARSE_MATRIX.f90:11-29):
-// the same words over a dictionary of distinct (re, im) pairs.  Keys are a
-// 64-bit mix of the two bit patterns; the inserting thread records the pair,
-// and the pack kernel checks every slot's pair bit for bit against its entry
-// (a hash collision between two pairs flags overflow: the plain arrays serve).
-__device__ __forceinline__ unsigned long long pair_key(double2 v) {
-  unsigned long long a = (unsigned long long)__double_as_longlong(v.x);
-  unsigned long long b = (unsigned long long)__double_as_longlong(v.y);
-  unsigned long long k = a ^ (b * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull + (a << 6) + (a >> 2));
-  return k == kDictEmpty ? 0x7ff8dead00000001ull : k;
-}
-
-static __global__ void __launch_bounds__(kBlock) k_dict_insert_c(const double2* __restrict__ vals, int64_t n,
-                                                          unsigned long long* table, double2* reps,
-                                                          unsigned int* overflow) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const double2 v = vals[i];
-    const unsigned long long key = pair_key(v);
-    if (!wave_key_leader(key)) continue;  // (pairs with equal keys are checked at pack time)
-    uint32_t h = dict_hash(key);
-    bool done = false;
-    for (int probe = 0; probe < kDictTable && !done; probe++) {
-      const unsigned long long cur = ((volatile unsigned long long*)table)[h];
-      if (cur == key) {
-        done = true;
-      } else if (cur == kDictEmpty) {
-        const unsigned long long prev = atomicCAS(table + h, kDictEmpty, key);
-        if (prev == kDictEmpty) {
-          reps[h] = v;  // the inserting thread records the pair
-          done = true;
-        } else if (prev == key) {
-          done = true;
-        } else {
-          h = (h + 1) & (kDictTable - 1);
-        }
-      } else {
-        h = (h + 1) & (kDictTable - 1);
-      }
-    }
-    if (!done) atomicOr(overflow, 1u);
-  }
-}
-
-static __global__ void __launch_bounds__(kBlock) k_dict_pack_c(const int32_t* __restrict__ cols,
-                                                        const double2* __restrict__ vals, int64_t n,
-                                                        const unsigned long long* __restrict__ table,
-                                                        const double2* __restrict__ reps,
-                                                        const uint8_t* __restrict__ tidx,
-                                                        uint32_t* __restrict__ words,
-                                                        unsigned int* overflow) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const double2 v = vals[i];
-    const unsigned long long key = pair_key(v);
-    uint32_t h = dict_hash(key);
-    while (table[h] != key) h = (h + 1) & (kDictTable - 1);  // present by construction
-    const double2 r = reps[h];
-    if (__double_as_longlong(r.x) != __double_as_longlong(v.x) ||
-        __double_as_longlong(r.y) != __double_as_longlong(v.y))
-      atomicOr(overflow, 1u);
-    words[i] = (uint32_t)cols[i] | ((uint32_t)tidx[h] << kPackShift);
-  }
 }
 
 template <bool HC, bool VC, int NT, class Epi, int CH = kChunk>
@@ -1468,29 +1232,6 @@ __global__ void __launch_bounds__(kBlock) k_kron_cols(KronArgs<HC> K, int64_t nu
   }
 }
 
-// -------------------------------- row split: columns the held rows gather
-// One bit per sector column, set for every column an off-diagonal element of
-// rows [row0, row0 + n) refers to (gen_row's elements: stored and matrix-free
-// alike).  The halo of a rank's row block for the split H·v (edgpu.dist).
-struct MarkAcc {
-  DevIndex idx;
-  uint32_t* mask;
-  __device__ __forceinline__ void diag(double, double) {}
-  __device__ __forceinline__ void off(uint32_t k, double, double) {
-    const uint32_t c = (uint32_t)idx(k);
-    atomicOr(mask + (c >> 5), 1u << (c & 31));
-  }
-};
-static __global__ void __launch_bounds__(kBlock) k_mark_cols(const EdModel* __restrict__ Mp,
-                                                      const uint32_t* __restrict__ map, int64_t n,
-                                                      DevIndex idx, uint32_t* mask) {
-  const EdModel& M = *Mp;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    MarkAcc a{idx, mask};
-    gen_row(M, map[i], a);
-  }
-}
-
 // ------------------------------------------------ GF seeds: c / c^+ |state>
 // One thread per source row; every target row is hit at most once (the
 // operator is injective on the Fock basis), so plain stores suffice.
@@ -1535,21 +1276,6 @@ __global__ void __launch_bounds__(kBlock) k_apply_op_acc(const uint32_t* __restr
   }
 }
 
-// ------------------------------------------------ GF pole sums (device G)
-// add_to_lanczos_gf_normal (ED_GF_NORMAL.f90:620-631) / _nonsu2
-// (ED_GF_NONSU2.f90:936-950): for every frequency i, fraction by fraction in
-// list order and pole by pole (j ascending), exactly the reference's sequence
-// of additions into G(i):
-//   G(i) = G(i) + peso_j / (iw_i - isign*de_j),  de_j = E_j - Ei,
-//   peso_j = (pesoBZ * z_j) * z_j,  iw = (0, wm_i) or (wr_i, eps).
-// One thread per frequency (Matsubara then real axis); the fraction and pole
-// data are wave-uniform (scalar loads); G stays in HBM across seeds.
-struct GfFrac {
-  int32_t p0, np, comp, isign;
-  double pr, pi, ei;  // pesoBZ (complex), Ei
-  double pad;
-};
-
 // Smith's complex division (the scaling gfortran/flang use for complex /)
 __device__ __forceinline__ double2 cdiv(double2 p, double a, double b) {
   if (fabs(b) <= fabs(a)) {
@@ -1558,41 +1284,6 @@ __device__ __forceinline__ double2 cdiv(double2 p, double a, double b) {
   }
   const double r = a / b, den = a * r + b;
   return make_double2((p.x * r + p.y) / den, (p.y * r - p.x) / den);
-}
-
-static __global__ void __launch_bounds__(kBlock) k_gf_poles(const GfFrac* __restrict__ fr, int nfrac,
-                                                     const double* __restrict__ E, const double* __restrict__ z,
-                                                     const double* __restrict__ wm, int lmats,
-                                                     const double* __restrict__ wr, int lreal, double eps,
-                                                     double2* __restrict__ gm, double2* __restrict__ gr) {
-  const int t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= lmats + lreal) return;
-  const bool mats = t < lmats;
-  const int i = mats ? t : t - lmats;
-  const double re_w = mats ? 0.0 : wr[i];   // iw = xi*wm(i) = (0, wm); dcmplx(wr(i), eps)
-  const double im_w = mats ? wm[i] : eps;
-  double2* G = mats ? gm : gr;
-  const int L = mats ? lmats : lreal;
-  int cur = -1;
-  double2 g = make_double2(0.0, 0.0);
-  for (int f = 0; f < nfrac; f++) {
-    const GfFrac q = fr[f];
-    if (q.comp != cur) {
-      if (cur >= 0) G[(int64_t)cur * L + i] = g;
-      cur = q.comp;
-      g = G[(int64_t)cur * L + i];
-    }
-    const double sgn = (double)q.isign;
-    for (int j = 0; j < q.np; j++) {
-      const double zj = z[q.p0 + j];
-      const double de = E[q.p0 + j] - q.ei;
-      const double2 peso = make_double2((q.pr * zj) * zj, (q.pi * zj) * zj);
-      const double d = sgn * de;
-      const double2 c = cdiv(peso, re_w - d, im_w);
-      g = make_double2(g.x + c.x, g.y + c.y);
-    }
-  }
-  if (cur >= 0) G[(int64_t)cur * L + i] = g;
 }
 
 // ------------------------------------------------------------ Lanczos misc

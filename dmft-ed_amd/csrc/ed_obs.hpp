@@ -42,7 +42,7 @@ struct ObsTerm {
   int32_t s0;
 };
 
-// What the compile step needs to know of a sector (ed_lib.hip fills it from
+// What the compile step needs to know of a sector (ed_hxv.hip fills it from
 // the sector object, the CPU tests from the model's numbers).
 struct ObsSector {
   int32_t ns;           // levels per spin

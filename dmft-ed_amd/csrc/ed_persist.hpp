@@ -429,7 +429,7 @@ __global__ void __launch_bounds__(NT) k_lanc_persist(const PersistRun<HC> a) {
   // complex vectors in register modes keep p = v_{k-1} in global memory (own
   // rows only, read once and written once per step, L2-resident): it frees
   // 4 VGPRs per row for the ELL words.  P is allocated with >= NT*RPT rows
-  // (p_rows, ed_lib.hip) so padding slots load and store without a guard.
+  // (p_rows, ed_lanczos.hip) so padding slots load and store without a guard.
   constexpr bool PG = (REG || KRC) && VC;
   // real vectors keep their own rows of r_k in registers; complex ones
   // re-read them from LDS (register budget of the ELL words)

@@ -1,8 +1,10 @@
 // ed_sector.hpp — internal header of the library's host translation units
-// (ed_lib.hip, ed_hxv.hip): the sector object, its stream-ordered allocator,
-// the per-launch predicates asked on every step (static inline here, in
-// namespace edg), and the declarations of the functions that cross the unit
-// boundary.
+// over the sector object (ed_lib.hip: life cycle and process-wide state;
+// ed_build.hip: the H builders; ed_hxv.hip: the H·v launchers; ed_lanczos.hip:
+// the Lanczos drivers; ed_eigh.hip: the thick-restart eigensolver): the
+// sector object, its stream-ordered allocator, the per-launch predicates
+// asked on every step (static inline here, in namespace edg), and the
+// declarations of the functions that cross a unit boundary.
 // Process-wide state (the error slot, the pinned pool, the resident_grid
 // cache, the singleton API's globals) is defined once, in ed_lib.hip, and
 // reached through the functions declared here and in ed_host.hpp.
@@ -255,6 +257,13 @@ struct DevFree {  // hipFreeAsync of one device block at scope exit
     if (p) (void)hipFreeAsync(p, st);
   }
 };
+// f(std::true_type) for complex(8) vectors, f(std::false_type) for real ones:
+// one generic lambda over the vector type where a call or a launch would
+// otherwise stand twice
+template <class F>
+static inline auto with_vc(bool vc, F&& f) {
+  return vc ? f(std::true_type{}) : f(std::false_type{});
+}
 // sub-arrays of a device slice of doubles start on 16-byte boundaries (double2)
 static inline size_t even(size_t q) { return (q + 1) & ~(size_t)1; }
 
@@ -272,7 +281,7 @@ static int64_t stored_mbytes(const ed_sector* s) {
   if (s->d_words) return s->padded * 4 + s->nrows * hv;
   return s->padded * (4 + hv) + s->nrows * hv;
 }
-// the two-segment form (ed_lib.hip: build_split) is built, and its launch
+// the two-segment form (ed_build.hip: build_split) is built, and its launch
 // shapes chosen, from this size on
 static constexpr int64_t kSplitMinBytes = (int64_t)192 << 20;
 
@@ -370,5 +379,16 @@ static int hxv_blocks(const ed_sector* s, int path, int vc = 0) {
 // {EpiStore, EpiTrlLoc, EpiLancA}, so every H·v kernel is compiled once
 template <bool VC, class Epi>
 int launch_hxv(ed_sector* s, int path, const void* x, Epi epi, hipStream_t st);
-// ed_lib.hip: the k_direct tables on first use of path 1
+// ed_build.hip: the builders sector_create (ed_lib.hip) runs, each on the
+// sector's stream, and the k_direct tables on first use of path 1
+int build_map(ed_sector* s);
+int build_stored(ed_sector* s);
+int build_kron(ed_sector* s);
+int build_direct(ed_sector* s);
 int ensure_direct(ed_sector* s, int path, hipStream_t caller = nullptr);
+// ed_lanczos.hip: the captured recurrence of a sector is dropped when its
+// options change (ed_sector_set_options, ed_lib.hip)
+void drop_graph(ed_sector* s);
+// ed_lanczos.hip: k_default_start on n doubles (the eigensolver's default
+// start vector is the Lanczos one; the kernel is compiled once, there)
+void launch_default_start(double* v, int64_t n, hipStream_t st);

@@ -65,66 +65,6 @@ __host__ __device__ inline int split_flags(const SplitSlice& q) { return q.nfl >
 constexpr int kSplitAGrid = 2048;  // k_spmv_sa blocks (a multiple of 8: one slice range per XCD)
 constexpr int kSplitGrid = 1280;   // k_spmv_sb blocks (a multiple of 8: one list per XCD; pass D's grid)
 
-// ---- build: segment A
-// nA[i] = in-block elements of row i; widthA[s] = max over slice s.  Also the
-// largest cross-block count of any row (atomicMax into *farmax).
-static __global__ void __launch_bounds__(kBlock) k_split_count_a(const int64_t* __restrict__ sptr,
-                                                          const uint32_t* __restrict__ words,
-                                                          const uint16_t* __restrict__ cnt,
-                                                          const uint32_t* __restrict__ map, int ns,
-                                                          int64_t dim, int64_t nslice, uint16_t* __restrict__ na,
-                                                          int32_t* __restrict__ widthA, int* farmax) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nslice * 64;
-       i += (int64_t)gridDim.x * kBlock) {
-    int c = 0, f = 0;
-    if (i < dim) {
-      const uint32_t blk = map[i] >> ns;
-      const uint32_t* wp = words + sptr[i >> 6] + (i & 63);
-      const int n = cnt[i];
-      for (int k = 0; k < n; k++) {
-        const uint32_t col = wp[64 * k] & kPackColMask;
-        if ((map[col] >> ns) == blk) c++;
-        else f++;
-      }
-      na[i] = (uint16_t)c;
-    }
-    const int w = wave_max(c);
-    const int fm = wave_max(f);
-    if ((threadIdx.x & 63) == 0) {
-      widthA[i >> 6] = w;
-      atomicMax(farmax, fm);
-    }
-  }
-}
-
-static __global__ void __launch_bounds__(kBlock) k_split_fill_a(const int64_t* __restrict__ sptr,
-                                                         const uint32_t* __restrict__ words,
-                                                         const uint16_t* __restrict__ cnt,
-                                                         const uint32_t* __restrict__ map, int ns,
-                                                         int64_t dim, int64_t nslice,
-                                                         const int64_t* __restrict__ sptrA,
-                                                         uint32_t* __restrict__ wordsA, uint32_t zpad) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nslice * 64;
-       i += (int64_t)gridDim.x * kBlock) {
-    const int64_t s = i >> 6;
-    const int wA = (int)((sptrA[s + 1] - sptrA[s]) >> 6);
-    uint32_t* ap = wordsA + sptrA[s] + (i & 63);
-    int k2 = 0;
-    if (i < dim) {
-      const uint32_t blk = map[i] >> ns;
-      const uint32_t* wp = words + sptr[s] + (i & 63);
-      const int n = cnt[i];
-      for (int k = 0; k < n; k++) {
-        const uint32_t wd = wp[64 * k];
-        if ((map[wd & kPackColMask] >> ns) == blk) ap[64 * (k2++)] = wd;
-      }
-    }
-    // padding: own column (or 0 past the last row), the dictionary's zero
-    const uint32_t pad = (uint32_t)(i < dim ? i : 0) | zpad;
-    for (; k2 < wA; k2++) ap[64 * k2] = pad;
-  }
-}
-
 // ---- build: segment B (one wavefront per slice of <= 128 rows, two
 // adjacent rows per lane).  FILL = false: nu, wl per slice; FILL = true: the
 // U list and the L words at the slice's offsets.  Each row's cross-block

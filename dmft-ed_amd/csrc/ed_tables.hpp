@@ -15,7 +15,7 @@
 // the same (popcount, Lz)) and off[idw] = number of sector states in the
 // blocks before idw.  Two 2^Ns tables (<= 256 KB each at Ns=16) replace the
 // O(log dim) search, and map[i] itself is produced on the device from
-// (off, rank) — see k_build_map in ed_kernels.hpp.
+// (off, rank) — see k_build_map in ed_build_kernels.hpp.
 #pragma once
 #include <stdint.h>
 

@@ -9,7 +9,7 @@
 // owns a contiguous block range, found by a binary search over the block
 // offsets), so a step is 7 launches for the whole farm and each launch is
 // as wide as the sum of the sectors' grids.  The per-sector arithmetic is
-// Trlan::step/orth's multi-kernel path (ed_lib.hip) on each sector's own
+// Trlan::step/orth's multi-kernel path (ed_eigh.hip) on each sector's own
 // grid G: the same CGS passes (cgs_body), coefficient sums (k_vdot_fin's
 // order), DGKS and local-only decisions, alpha/beta and V_{j+1}; the host
 // runs trlan_core's / probe_screen's per-sector logic on the mailboxes

@@ -1,6 +1,6 @@
 """Host restatements for the susceptibility tests (test infrastructure only).
 
-chi_poles_host   the arithmetic of k_chi_poles (csrc/ed_chi.hpp) in numpy:
+chi_poles_host   the arithmetic of k_chi_poles (csrc/ed_poles.hip) in numpy:
                  the same formulas in the same order of additions, vectorised
                  over the grid points only.
 numpy_seeds      the seeds of ed_sector_seed_diag: the factor summed in level

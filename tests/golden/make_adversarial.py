@@ -1,5 +1,5 @@
 """Generate tests/golden/adversarial_probe.json: near-cut degenerate sectors
-for the degeneracy probe of the device eigensolver (ed_lib.hip trlan_run /
+for the degeneracy probe of the device eigensolver (ed_eigh.hip trlan_run /
 probe_screen; reference call site ED_DIAG.f90:88-101, Neigen=6).
 
 TEST INFRASTRUCTURE ONLY — run in the CPU container:

@@ -3,7 +3,7 @@ that records its fixture (tests/golden/make_persist_mode4_parent.py).
 
 Norb=1 normal-mode sectors, the smallest that reach each code shape of the
 persistent Kronecker-register Lanczos kernel (MODE 4, real vectors): hop-list
-width E and rows per thread RPT as pkr_geom (csrc/ed_lib.hip) derives them
+width E and rows per thread RPT as pkr_geom (csrc/ed_lanczos.hip) derives them
 from DimUp x DimDw and the hop degrees.
 """
 from math import comb

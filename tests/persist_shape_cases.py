@@ -23,7 +23,7 @@ the multi-kernel run, which differ only in summation order, are 1.5e-5 to
 2.4e-5 apart by step 40 (1e-13 from the reference at step 24), so it cannot
 be held to the multi-kernel comparison; nb8 (2,1) takes its place.
 
-How a form is forced (persist_mode_derive, csrc/ed_lib.hip):
+How a form is forced (persist_mode_derive, csrc/ed_lanczos.hip):
   mode 0  stored sector, option persist_stored
   mode 1  matrix-free sector with Kronecker form, option no_preg
   mode 2  stored sector, option no_pkron (else a real Norb=1 H takes MODE 4)

@@ -161,6 +161,53 @@ def test_lanc_tridiag_batch_matches_single():
                 np.testing.assert_array_equal(b1, b[k])
 
 
+@pytest.mark.parametrize("options", [(), ("no_batch",), ("no_persist",)], ids=["default", "no_batch", "no_persist"])
+def test_lanc_tridiag_entries_agree(options):
+    """The three entries of the single-run tridiagonalisation give the same
+    bits for every seed: the batch entry (one persistent launch under (), the
+    per-seed loop under no_batch and no_persist), the device-vector entry and
+    the host-vector entry (Sector.lanc_tridiag).  Within one set of options
+    all three run the same recurrence on the same start vector, so alpha, beta
+    and nlanc are compared with assert_array_equal; across options nothing is
+    compared (the persistent and the multi-kernel recurrence sum in different
+    orders).  lanc_geom says which recurrence ran: persistent unless
+    no_persist, so the three cases cannot be one branch run three times.
+    The sector of test_lanc_tridiag_batch_matches_single (nonsu2 Norb=1
+    Nbath=6 (6, 0), 3,003 rows) runs the multi-kernel recurrence under every
+    option, so this test takes the smallest sector of persist_shape_cases.py
+    that is persistent by default: nb3_2_2, normal Norb=1 Nbath=3 (2, 2),
+    stored, real, 36 rows (nitermax 40 is past its dimension: the runs end
+    early, and nlanc is compared too)."""
+    import torch
+
+    from edgpu.gf import _tridiag_batch, _tridiag_dev
+    from edgpu.hamiltonian import Sector
+
+    cfg = make_config(Norb=1, Nbath=3)
+    nseed, nitermax = 3, 40
+    with Sector(cfg, 2, 2, stored=True, real=True, options=options) as S:
+        assert S.dim == 36
+        g = torch.Generator(device="cuda:0").manual_seed(5)
+        for cplx in (False, True):
+            mode = S.lanc_geom(real=not cplx)["mode"]
+            if "no_persist" in options:
+                assert mode == -1
+            else:
+                assert mode >= 0
+            dt = torch.complex128 if cplx else torch.float64
+            seeds = torch.rand(nseed, S.dim, dtype=dt, device="cuda:0", generator=g)
+            seeds = (seeds / torch.linalg.vector_norm(seeds, dim=1, keepdim=True)).contiguous()
+            host = seeds.cpu().numpy()
+            a, b, n = _tridiag_batch(S, seeds, nitermax, not cplx, 1e-13)
+            assert np.all(n > 0) and np.any(a != 0)
+            for k in range(nseed):
+                for a1, b1, n1 in (_tridiag_dev(S, seeds[k], nitermax, not cplx, 1e-13),
+                                   S.lanc_tridiag(host[k], nitermax, 1e-13, real=not cplx)):
+                    assert n1 == n[k]
+                    np.testing.assert_array_equal(a1, a[k])
+                    np.testing.assert_array_equal(b1, b[k])
+
+
 def test_device_pole_sums_match_reference_loop():
     """ed_gf_add_poles (device G, one launch for many continued fractions)
     against the reference's loop written out in numpy (ED_GF_NORMAL.f90:620-631:

@@ -1,4 +1,4 @@
-"""Launch path of the persistent Lanczos kernel (csrc/ed_lib.hip,
+"""Launch path of the persistent Lanczos kernel (csrc/ed_lanczos.hip,
 csrc/ed_persist.hpp): a single run is one kernel on the stream (lanc_run) or
 one kernel and the download of its LancState (lanc_tridiag, lanc_tridiag_dev,
 lanc_eigh); the batched launch still downloads alpha, beta and the states.

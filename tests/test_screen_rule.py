@@ -1,4 +1,4 @@
-"""The degeneracy probe's screening decision (probe_screen, ed_lib.hip) in a
+"""The degeneracy probe's screening decision (probe_screen, ed_eigh.hip) in a
 numpy restatement, on the adversarial near-cut sectors of
 tests/golden/adversarial_probe.json (make_adversarial.py; ED_DIAG.f90:88-101
 Neigen=6).
