@@ -417,6 +417,14 @@ int ed_gpu_hxv(const int32_t* nloc, const double* v, double* hv) {
   return ed_sector_hxv(g_cur, *nloc, v, hv);
 }
 
+int ed_gpu_nnz(int64_t* nnz) {
+  if (!g_cur) return fail(ED_ERR_STATE, "no current sector");
+  if (!nnz) return fail(ED_ERR_ARG, "null");
+  if (!(g_cur->flags & ED_STORED)) return fail(ED_ERR_STATE, "sector was built without ED_STORED");
+  *nnz = g_cur->nnz;
+  return ED_OK;
+}
+
 int ed_gpu_dump_csr(int64_t* rowptr, int32_t* cols, double* vals) {
   if (!g_cur) return fail(ED_ERR_STATE, "no current sector");
   return ed_sector_dump_csr(g_cur, rowptr, cols, vals);

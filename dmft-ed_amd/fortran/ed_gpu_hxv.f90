@@ -122,6 +122,18 @@ module ED_GPU_HXV
        complex(c_double_complex), intent(out) :: evecs(*)
        integer(c_int32_t), intent(out) :: nconv
      end function ed_gpu_eigh
+     ! sp_dump_matrix(spH0,Hmat) of a stored sector as CSR in spH0's row order:
+     ! rowptr(rows held + 1), cols(nnz) 0-based, vals(nnz), nnz from ed_gpu_nnz
+     integer(c_int) function ed_gpu_nnz(nnz) bind(C, name="ed_gpu_nnz")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: nnz
+     end function ed_gpu_nnz
+     integer(c_int) function ed_gpu_dump_csr(rowptr, cols, vals) bind(C, name="ed_gpu_dump_csr")
+       import :: c_int, c_int32_t, c_int64_t, c_double_complex
+       integer(c_int64_t), intent(out) :: rowptr(*)
+       integer(c_int32_t), intent(out) :: cols(*)
+       complex(c_double_complex), intent(out) :: vals(*)
+     end function ed_gpu_dump_csr
      integer(c_int) function ed_gpu_delete_sector() bind(C, name="ed_gpu_delete_sector")
        import :: c_int
      end function ed_gpu_delete_sector
@@ -140,6 +152,7 @@ module ED_GPU_HXV
   public :: ed_gpu_init, ed_gpu_set_device, ed_gpu_build_sector, ed_gpu_vecdim, ed_gpu_hxv
   public :: ed_gpu_lanc_eigh, ed_gpu_lanc_tridiag, ed_gpu_eigh, ed_gpu_delete_sector, ed_gpu_finalize
   public :: ed_gpu_build_sector_rows, ed_gpu_mpi_split, ed_gpu_hxv_mpi
+  public :: ed_gpu_nnz, ed_gpu_dump_csr
   public :: gpuMatVec_cc, gpuMatVec_mpi_cc
   public :: ed_gpu_check
   public :: ed_gpu_pack_params
@@ -227,18 +240,28 @@ contains
 
   !> Pack the reference's model state (impHloc, dmft_bath components and the
   !> interaction constants) into the C struct.  Arrays use the reference's
-  !> shapes: impHloc(Nspin,Nspin,Norb,Norb); e,v,u,d(Nspin,Norb|1,Nbath).
+  !> shapes (dmft_aux.f90:13-44): impHloc(Nspin,Nspin,Norb,Norb);
+  !> e,v,u,d(Nspin,Norb|1,Nbath); h(Nspin,Nspin,Norb,Norb,Nbath); vr(Nbath).
+  !> Every bath component is optional: pass dmft_bath%e ... dmft_bath%vr as
+  !> they are, an unallocated component counts as absent (a replica bath has
+  !> no e/v/u/d, the others no h/vr).  Sizes beyond the struct's (which
+  !> ed_gpu_init refuses) are recorded in norb/nspin/nbath but not copied.
   subroutine ed_gpu_pack_params(p, Norb, Nspin, Nbath, ed_mode, bath_type, hfmode, &
-       Uloc, Ust, Jh, Jx, Jp, xmu, impHloc, e, v, u, d)
+       Uloc, Ust, Jh, Jx, Jp, xmu, impHloc, e, v, u, d, h, vr, Jz_basis)
     type(ed_params_t), intent(out)   :: p
     integer, intent(in)              :: Norb, Nspin, Nbath
     character(len=*), intent(in)     :: ed_mode, bath_type
     logical, intent(in)              :: hfmode
     real(8), intent(in)              :: Uloc(3), Ust, Jh, Jx, Jp, xmu
     complex(8), intent(in)           :: impHloc(:,:,:,:)
-    real(8), intent(in)              :: e(:,:,:), v(:,:,:)
+    real(8), intent(in), optional    :: e(:,:,:), v(:,:,:)
     real(8), intent(in), optional    :: u(:,:,:), d(:,:,:)
-    integer :: is, js, io, jo, k
+    complex(8), intent(in), optional :: h(:,:,:,:,:), vr(:)
+    logical, intent(in), optional    :: Jz_basis
+    integer :: is, js, io, jo, k, no, nsp, nb
+    no  = min(Norb, ED_MAX_NORB)
+    nsp = min(Nspin, ED_MAX_NSPIN)
+    nb  = min(Nbath, ED_MAX_NBATH)
     p%norb = Norb ; p%nspin = Nspin ; p%nbath = Nbath
     select case (trim(ed_mode))
     case ("superc") ; p%ed_mode = 1
@@ -256,30 +279,58 @@ contains
     p%bath_e = 0d0 ; p%bath_v = 0d0 ; p%bath_u = 0d0 ; p%bath_d = 0d0
     p%bath_h_re = 0d0 ; p%bath_h_im = 0d0 ; p%bath_vr_re = 0d0 ; p%bath_vr_im = 0d0
     p%jz_basis = 0 ; p%pad_ = 0
-    do is = 1, Nspin
-       do js = 1, Nspin
-          do io = 1, Norb
-             do jo = 1, Norb
+    if (present(Jz_basis)) p%jz_basis = merge(1, 0, Jz_basis)
+    do is = 1, nsp
+       do js = 1, nsp
+          do io = 1, no
+             do jo = 1, no
                 p%imphloc_re(jo,io,js,is) = dble(impHloc(is,js,io,jo))
                 p%imphloc_im(jo,io,js,is) = aimag(impHloc(is,js,io,jo))
              enddo
           enddo
        enddo
     enddo
-    do is = 1, Nspin
-       do io = 1, size(e,2)
-          do k = 1, Nbath
-             p%bath_e(k,io,is) = e(is,io,k)
-             if (present(d)) p%bath_d(k,io,is) = d(is,io,k)
+    if (present(e)) call pack3(p%bath_e, e)
+    if (present(v)) call pack3(p%bath_v, v)
+    if (present(u)) call pack3(p%bath_u, u)
+    if (present(d)) call pack3(p%bath_d, d)
+    if (present(h)) then
+       do is = 1, nsp
+          do js = 1, nsp
+             do io = 1, no
+                do jo = 1, no
+                   do k = 1, nb
+                      p%bath_h_re(k,jo,io,js,is) = dble(h(is,js,io,jo,k))
+                      p%bath_h_im(k,jo,io,js,is) = aimag(h(is,js,io,jo,k))
+                   enddo
+                enddo
+             enddo
           enddo
        enddo
-       do io = 1, size(v,2)
-          do k = 1, Nbath
-             p%bath_v(k,io,is) = v(is,io,k)
-             if (present(u)) p%bath_u(k,io,is) = u(is,io,k)
-          enddo
+    endif
+    if (present(vr)) then
+       do k = 1, nb
+          p%bath_vr_re(k) = dble(vr(k))
+          p%bath_vr_im(k) = aimag(vr(k))
        enddo
-    enddo
+    endif
+
+  contains
+
+    ! a(is, io, k) -> dst(k, io, is); the second extent is Norb, or 1 for the
+    ! e/d of a hybrid bath
+    subroutine pack3(dst, a)
+      real(c_double), intent(inout) :: dst(ED_MAX_NBATH,ED_MAX_NORB,ED_MAX_NSPIN)
+      real(8), intent(in)           :: a(:,:,:)
+      integer :: i1, i2, i3
+      do i1 = 1, nsp
+         do i2 = 1, min(size(a,2), ED_MAX_NORB)
+            do i3 = 1, nb
+               dst(i3,i2,i1) = a(i1,i2,i3)
+            enddo
+         enddo
+      enddo
+    end subroutine pack3
   end subroutine ed_gpu_pack_params
 
 end module ED_GPU_HXV

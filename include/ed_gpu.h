@@ -29,7 +29,8 @@
  *                                (safe after a direct build, unlike the reference)
  *   ed_gpu_vecdim             <- vecDim_Hv_sector       ED_HAMILTONIAN.f90:126-149
  *   ed_gpu_dump_csr           <- sp_dump_matrix         ED_SPARSE_MATRIX.f90:331-388
- *                                (row-of-arrays order of sp_insert_element :249-320)
+ *                                (row-of-arrays order of sp_insert_element :249-320;
+ *                                ed_gpu_nnz sizes its arrays)
  *   ed_gpu_lanc_eigh          <- sp_lanc_eigh (SciFortran; spec .repo/PLAIN_LANCZOS.f90:286-385)
  *   ed_gpu_lanc_tridiag       <- sp_lanc_tridiag (SciFortran; spec .repo/PLAIN_LANCZOS.f90:154-180)
  *   ed_gpu_eigh               <- sp_eigh (ARPACK; called at ED_DIAG.f90:145-167)
@@ -616,6 +617,10 @@ int ed_gpu_mpi_split(int64_t dim, int32_t rank, int32_t size, int64_t* row0, int
  * reference's serial element order (spMatVec_cc); the reference's MPI kernel
  * adds the local-column elements first, so the two differ by rounding. */
 int ed_gpu_hxv_mpi(const int32_t* nloc, const double* vin, double* hv);
+/* Stored elements (diagonal included) of the rows the current sector holds:
+ * the length a caller gives cols/vals of ed_gpu_dump_csr (rowptr: rows + 1).
+ * ED_ERR_STATE without a current sector or on one built without ED_STORED. */
+int ed_gpu_nnz(int64_t* nnz);
 int ed_gpu_dump_csr(int64_t* rowptr, int32_t* cols, double* vals);
 int ed_gpu_lanc_eigh(int32_t nitermax, double threshold, int32_t ncheck, double* egs,
                      double* vect, int32_t* nlanc);
