@@ -6,6 +6,8 @@
 #include "ed_sector.hpp"
 #include "ed_persist.hpp"
 #include "ed_hosteig.hpp"
+#include "ed_multi.hpp"
+#include "ed_lockstep_groups.hpp"
 
 using namespace edg;
 
@@ -881,6 +883,138 @@ int ed_sector_lanc_tridiag_batch(ed_sector* s, int32_t vtype, int32_t nseed, con
   for (int k = 0; k < nseed; k++) {
     // a run that never broke down ends with st->iter = nitermax
     const double* a = hab.data() + (size_t)k * bt.ldab;
+    unpack_tridiag(a, a + nitermax + 2, hst[k].iter, nitermax, alfa + (size_t)k * nitermax,
+                   beta + (size_t)k * nitermax, nlanc ? nlanc + k : nullptr);
+  }
+  return ED_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------- lockstep multi-vector runs
+// Workspace of one group of at most `width` runs (ed_multi.hpp): the
+// row-interleaved blocks R, P, W, one LancState per run, the block partials
+// of a pass ([width][np]) and alpha | beta of every run (run v at ab + v*ldab,
+// beta nitermax + 2 behind alpha, as PersistBatch lays them out).
+struct LockWS {
+  void *R, *P, *W;
+  LancState* st;
+  double *partials, *ab;
+  int64_t ldab;
+  int np;
+};
+// grid of the element-wise passes (init, part B): enough blocks to fill the
+// chip; their partials are summed by one block per run
+static constexpr int kLockPassGrid = 4096;
+static int lock_pass_grid(int64_t n) { return std::min(grid_for(n), kLockPassGrid); }
+
+// nitermax steps of NV runs in lockstep from seeds (NV vectors of dim, the
+// batch entry's layout).  One step: block H·X with the Lanczos epilogue, its
+// finish, part B, its finish — four launches in stream order (a capture of
+// them would have no parallel branch; they are launched directly because the
+// workspace is allocated per call, and a captured graph bakes its pointers in).
+template <bool VC, int NV>
+static int lockstep_group(ed_sector* s, const LockWS& w, const void* seeds, int nitermax, double thresh,
+                          hipStream_t st) {
+  using V = val_t<VC>;
+  const int64_t n = s->dim * NV, boff = (int64_t)nitermax + 2;
+  const int g0 = lock_pass_grid(s->dim), g1 = hxv_mv_blocks(s), g2 = lock_pass_grid(n);
+  HIPCK(hipMemsetAsync(w.ab, 0, (size_t)NV * w.ldab * sizeof(double), st));  // alpha | beta
+  hipLaunchKernelGGL((k_lanc_init_mv<VC, NV>), dim3(g0), dim3(kBlock), 0, st, (const V*)seeds, (V*)w.R, (V*)w.P,
+                     s->dim, w.partials);
+  hipLaunchKernelGGL(k_lanc_fin_mv<0>, dim3(NV), dim3(kBlock), 0, st, w.partials, g0, w.st, w.ab, w.ldab, boff, thresh);
+  HIPCK(hipGetLastError());
+  EpiLancAMV<VC, NV> e{};
+  e.st = w.st;
+  e.P = (V*)w.P;
+  e.W = (V*)w.W;
+  e.partials = w.partials;
+  for (int k = 0; k < nitermax; k++) {
+    CK((launch_hxv_mv<VC, NV>(s, w.R, e, st)));
+    hipLaunchKernelGGL(k_lanc_fin_mv<1>, dim3(NV), dim3(kBlock), 0, st, w.partials, g1, w.st, w.ab, w.ldab, boff, thresh);
+    hipLaunchKernelGGL((k_lanc_b_mv<VC, NV>), dim3(g2), dim3(kBlock), 0, st, (const V*)w.W, (const V*)w.P, (V*)w.R, n,
+                       w.st, w.partials);
+    hipLaunchKernelGGL(k_lanc_fin_mv<2>, dim3(NV), dim3(kBlock), 0, st, w.partials, g2, w.st, w.ab, w.ldab, boff, thresh);
+  }
+  HIPCK(hipGetLastError());
+  return ED_OK;
+}
+
+template <bool VC>
+static int lockstep_group_nv(ed_sector* s, int nv, const LockWS& w, const void* seeds, int nitermax, double thresh,
+                             hipStream_t st) {
+  switch (nv) {
+    case 8: return lockstep_group<VC, 8>(s, w, seeds, nitermax, thresh, st);
+    case 4: return lockstep_group<VC, 4>(s, w, seeds, nitermax, thresh, st);
+    case 2: return lockstep_group<VC, 2>(s, w, seeds, nitermax, thresh, st);
+    default: return lockstep_group<VC, 1>(s, w, seeds, nitermax, thresh, st);
+  }
+}
+
+extern "C" {
+
+// sp_lanc_tridiag (.repo/PLAIN_LANCZOS.f90:87-118) for nseed start vectors
+// that advance together: the seeds are cut into groups of 8, 4, 2, 1
+// (ed_lockstep_groups.hpp) and each group's vectors are interleaved by row, so
+// one pass over the stored H (k_spmv_mv, ed_multi.hpp) serves the whole group.
+// Per run the arithmetic is lanc_iter's; the two dot products of a step are
+// summed over other block shapes, so alpha and beta agree with
+// ed_sector_lanc_tridiag_batch to rounding, not bit for bit.
+int ed_sector_lanc_tridiag_lockstep(ed_sector* s, int32_t vtype, int32_t nseed, const void* v0_dev,
+                                    int32_t nitermax, double threshold, double* alfa, double* beta,
+                                    int32_t* nlanc) {
+  if (nseed < 1) return fail(ED_ERR_ARG, "nseed must be positive");
+  if (nitermax < 1) return fail(ED_ERR_ARG, "nitermax must be positive");
+  if (vtype != 0 && vtype != 1) return fail(ED_ERR_ARG, "vtype must be 0 (real) or 1 (complex)");
+  if (!s || !v0_dev || !alfa || !beta) return fail(ED_ERR_ARG, "null");
+  if (vtype == 0 && s->hc) return fail(ED_ERR_ARG, "complex H needs vtype=1");
+  const size_t vs = vtype ? 16 : 8;
+  if ((uintptr_t)v0_dev & (vs - 1)) return fail(ED_ERR_ARG, "v0_dev must be aligned to its element type");
+  CK(mv_sector_check(s));
+  HIPCK(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  std::vector<int> first(lockstep_max_groups(nseed)), width(first.size());
+  const int ngroup = lockstep_groups(nseed, first.data(), width.data());
+  // one group's workspace, sized by the widest (the first); the later groups reuse it
+  const int w0 = width[0];
+  LockWS w;
+  w.ldab = 2 * ((int64_t)nitermax + 2);
+  w.np = std::max(hxv_mv_blocks(s), lock_pass_grid(s->dim * w0));
+  // freed on the stream at every return, an allocation failure's included
+  DevFree fR{nullptr, st}, fP{nullptr, st}, fW{nullptr, st}, fst{nullptr, st}, fpart{nullptr, st}, fab{nullptr, st};
+  HIPCK(hipMallocAsync(&fR.p, (size_t)s->dim * w0 * vs, st));
+  HIPCK(hipMallocAsync(&fP.p, (size_t)s->dim * w0 * vs, st));
+  HIPCK(hipMallocAsync(&fW.p, (size_t)s->dim * w0 * vs, st));
+  HIPCK(hipMallocAsync(&fst.p, (size_t)w0 * sizeof(LancState), st));
+  HIPCK(hipMallocAsync(&fpart.p, (size_t)w0 * w.np * sizeof(double), st));
+  HIPCK(hipMallocAsync(&fab.p, (size_t)w0 * w.ldab * sizeof(double), st));
+  w.R = fR.p;
+  w.P = fP.p;
+  w.W = fW.p;
+  w.st = (LancState*)fst.p;
+  w.partials = (double*)fpart.p;
+  w.ab = (double*)fab.p;
+  std::vector<double> hab((size_t)nseed * w.ldab);
+  std::vector<LancState> hst(nseed);
+  int rc = ED_OK;
+  for (int g = 0; g < ngroup && rc == ED_OK; g++) {
+    const void* seeds = (const unsigned char*)v0_dev + (size_t)first[g] * s->dim * vs;
+    rc = with_vc(vtype != 0, [&](auto c) {
+      return lockstep_group_nv<decltype(c)::value>(s, width[g], w, seeds, nitermax, threshold, st);
+    });
+    if (rc != ED_OK) break;
+    // (stream order: the copies are complete before the next group clears the block)
+    hipError_t e1 = hipMemcpyAsync(hab.data() + (size_t)first[g] * w.ldab, w.ab, (size_t)width[g] * w.ldab * 8,
+                                   hipMemcpyDeviceToHost, st);
+    hipError_t e2 = hipMemcpyAsync(hst.data() + first[g], w.st, (size_t)width[g] * sizeof(LancState),
+                                   hipMemcpyDeviceToHost, st);
+    if (e1 != hipSuccess || e2 != hipSuccess)
+      rc = fail(ED_ERR_HIP, std::string("lockstep download -> ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+  }
+  HIPCK(hipStreamSynchronize(st));
+  CK(rc);
+  for (int k = 0; k < nseed; k++) {
+    const double* a = hab.data() + (size_t)k * w.ldab;
     unpack_tridiag(a, a + nitermax + 2, hst[k].iter, nitermax, alfa + (size_t)k * nitermax,
                    beta + (size_t)k * nitermax, nlanc ? nlanc + k : nullptr);
   }

@@ -379,6 +379,14 @@ static int hxv_blocks(const ed_sector* s, int path, int vc = 0) {
 // {EpiStore, EpiTrlLoc, EpiLancA}, so every H·v kernel is compiled once
 template <bool VC, class Epi>
 int launch_hxv(ed_sector* s, int path, const void* x, Epi epi, hipStream_t st);
+// ed_multi.hip: the block stored kernel k_spmv_mv (ed_multi.hpp) on x, a
+// dim x NV row-interleaved block; instantiated there for VC in {false, true}
+// x NV in {1, 2, 4, 8} x {EpiStoreMV, EpiLancAMV}.  hxv_mv_blocks: its grid;
+// mv_sector_check: ED_ERR_UNSUPPORTED unless the sector is stored and whole
+template <bool VC, int NV, class Epi>
+int launch_hxv_mv(ed_sector* s, const void* x, Epi epi, hipStream_t st);
+int hxv_mv_blocks(const ed_sector* s);
+int mv_sector_check(const ed_sector* s);
 // ed_build.hip: the builders sector_create (ed_lib.hip) runs, each on the
 // sector's stream, and the k_direct tables on first use of path 1
 int build_map(ed_sector* s);

@@ -68,6 +68,8 @@ SIGNATURES = {
     "ed_sector_expect": ([_P, _i32, _P, _i32, _P, _P, _P, _P, _P], ctypes.c_int),
     "ed_sector_lanc_tridiag_dev": ([_P, _i32, _P, _i32, _f64, _P, _P, _P], ctypes.c_int),
     "ed_sector_lanc_tridiag_batch": ([_P, _i32, _i32, _P, _i32, _f64, _P, _P, _P], ctypes.c_int),
+    "ed_sector_hxv_multi": ([_P, _i32, _i32, _P, _P, _P], ctypes.c_int),
+    "ed_sector_lanc_tridiag_lockstep": ([_P, _i32, _i32, _P, _i32, _f64, _P, _P, _P], ctypes.c_int),
     "ed_tridiag_poles": ([_i32, _P, _P, _P, _P, _P], ctypes.c_int),
     "ed_gf_add_poles": ([_i32, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _i32, _f64, _P, _P, _P],
                         ctypes.c_int),

@@ -71,6 +71,7 @@ class ChiOptions:
     wfin: float = 5.0
     threshold: float = 1e-13      # sp_lanc_tridiag breakdown test
     sparse_H: bool = True         # ed_sparse_H
+    lockstep: bool = False        # GFOptions.lockstep: the seeds of one sector advance together
 
     @property
     def ltau(self) -> int:
@@ -387,7 +388,8 @@ def build_chi(cfg: EDConfig, states: StateList, copt: Optional[ChiOptions] = Non
             def run(St, make, queue):
                 """The seeds make(rows) of sector St; queue[s]: the fractions of seed s as (name, comp, isign)."""
                 for s, norm2, a, b, nl, E, z in seed_fractions(St, make, len(queue), cplx,
-                                                               min(St.dim, copt.lanc_nGFiter), copt.threshold):
+                                                               min(St.dim, copt.lanc_nGFiter), copt.threshold,
+                                                               lockstep=copt.lockstep):
                     for name, comp, isign in queue[s]:
                         if record is not None:
                             record.append(dict(name=name, comp=comp, state=k, isector=isec, norm2=norm2, alfa=a,

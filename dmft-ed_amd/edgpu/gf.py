@@ -74,6 +74,12 @@ class GFOptions:
     # summation order of norm2 differs from the per-seed chain.  superc: one
     # ed_sector_seed_plan call per (kept state, target sector, vector type)
     fused_seeds: bool = False
+    # the seeds of a target sector whose Lanczos runs are not persistent (the
+    # large sectors) advance in lockstep groups of 8, 4, 2, 1 through one block
+    # H·X per Krylov step (ed_sector_lanc_tridiag_lockstep) instead of one
+    # after the other.  alfa and beta then differ from the serial runner's by
+    # the summation order of the two dot products of a step
+    lockstep: bool = False
 
 
 # fused_seeds: a stacked seed buffer (one batched Lanczos launch) stays under
@@ -488,9 +494,40 @@ def _run_job(cfg, states, gopt, job, cache, poles, record, zeta):
     poles.add(comp, _peso(cfg)(states, k, weight, norm2, zeta), e_i, E, z, isign)
 
 
-def _tridiag_batch(S: Sector, seeds, nlanc: int, real: bool, threshold: float):
-    """sp_lanc_tridiag of every seed (rows of the contiguous `seeds` tensor) on S."""
+# complex(8) vectors go in lockstep only on sectors of at most this many rows:
+# the measured table of DESIGN.md §15 (profiles/lockstep/INDEX.md) has them
+# faster at 853,776 rows and slower at 10,306,296; nothing between was measured
+LOCKSTEP_COMPLEX_MAX_DIM = 853776
+
+
+def _lockstep_seeds(S: Sector, nseed: int, real: bool) -> int:
+    """How many of the nseed seeds of S, from the first, the lockstep entry
+    takes; the others go through ed_sector_lanc_tridiag_batch.  None unless the
+    sector holds the whole stored matrix and its Lanczos runs of this vector
+    type are not persistent (those go in one batched launch, one workgroup per
+    seed, already).  Then the group widths that measured faster than the
+    sequential runs: 8, 4 and 2, so an odd seed count leaves
+    its width-1 tail to the batch entry; complex vectors only up to
+    LOCKSTEP_COMPLEX_MAX_DIM rows."""
+    if not (S.stored_whole and S.lanc_mode(real=real) < 0):
+        return 0
+    if not real and S.dim > LOCKSTEP_COMPLEX_MAX_DIM:
+        return 0
+    return nseed - nseed % 2
+
+
+def _tridiag_batch(S: Sector, seeds, nlanc: int, real: bool, threshold: float, lockstep: bool = False):
+    """sp_lanc_tridiag of every seed (rows of the contiguous `seeds` tensor) on
+    S; `lockstep`: the first _lockstep_seeds of them through
+    Sector.lanc_tridiag_lockstep."""
     k = seeds.shape[0]
+    head = _lockstep_seeds(S, k, real) if lockstep else 0
+    if head == k:
+        return S.lanc_tridiag_lockstep(seeds, nlanc, threshold)
+    if head:
+        first, rest = S.lanc_tridiag_lockstep(seeds[:head], nlanc, threshold), _tridiag_batch(S, seeds[head:], nlanc, real,
+                                                                                              threshold)
+        return tuple(np.concatenate(pair) for pair in zip(first, rest))
     a = np.zeros((k, nlanc))
     b = np.zeros((k, nlanc))
     n = np.zeros(k, dtype=np.int32)
@@ -571,7 +608,8 @@ def _fused_seeds(cfg, states, jobs, members, cache, cplx: bool, mixed: bool = Fa
     return rows, out, norms
 
 
-def seed_fractions(S: Sector, make, nseed: int, cplx: bool, nlanc: int, threshold: float, chunked: bool = True):
+def seed_fractions(S: Sector, make, nseed: int, cplx: bool, nlanc: int, threshold: float, chunked: bool = True,
+                   lockstep: bool = False):
     """From seed calls to continued fractions, for build_gf, build_gf_superc
     and build_chi.  make(rows) -> (device tensor, norm2) builds the normalised
     seeds `rows` (a range of 0..nseed-1) of sector S as the tensor's rows;
@@ -579,7 +617,8 @@ def seed_fractions(S: Sector, make, nseed: int, cplx: bool, nlanc: int, threshol
     are dropped (no fraction), the others of a tensor tridiagonalised in one
     batched launch.  Yields (seed index, norm2, alfa, beta, nlanc found, E, z)
     in seed order, E and z(1, j) from `tridiag_poles` over all `nlanc` entries
-    (the reference diagonalises them all; unset ones stay 0)."""
+    (the reference diagonalises them all; unset ones stay 0).  `lockstep`:
+    GFOptions.lockstep."""
     import torch
 
     step = max(1, SEED_BUFFER_BYTES // (S.dim * (16 if cplx else 8))) if chunked else max(1, nseed)
@@ -593,7 +632,7 @@ def seed_fractions(S: Sector, make, nseed: int, cplx: bool, nlanc: int, threshol
         # the library reads the seeds on the sector's own (non-blocking) stream:
         # what torch's stream still does to them must be complete first
         torch.cuda.current_stream(stacked.device).synchronize()
-        a, b, nl = _tridiag_batch(S, stacked, nlanc, not cplx, threshold)
+        a, b, nl = _tridiag_batch(S, stacked, nlanc, not cplx, threshold, lockstep)
         for row, q in enumerate(keep):
             E, z = tridiag_poles(a[row], b[row], nlanc, first_row=True)
             yield q0 + q, float(n2[q]), a[row], b[row], int(nl[row]), E, z
@@ -637,7 +676,7 @@ def _run_jobs_batched(cfg, states, gopt, jobs, todo, device, poles, zeta, record
             nlanc = min(HJ.dim, gopt.lanc_nGFiter)
             # only the fused seeds are chunked: the others exist one by one before they are stacked
             for i, norm2, a, b, nl, E, z in seed_fractions(HJ, make, len(members), cplx, nlanc, gopt.threshold,
-                                                           chunked=gopt.fused_seeds):
+                                                           chunked=gopt.fused_seeds, lockstep=gopt.lockstep):
                 n = held[i]
                 job = jobs[n]
                 if record is not None:

@@ -246,6 +246,57 @@ class Sector:
         return dict(mode=int(g[0]), threads=int(g[1]), rpt=int(g[2]), width=int(g[3]), lds=int(g[4]),
                     hc=bool(g[5]))
 
+    # ------------------------------------------------- blocks of vectors
+    @property
+    def stored_whole(self) -> bool:
+        """The sector holds the whole stored matrix: what the block H·X kernel
+        (hxv_multi, lanc_tridiag_lockstep) reads."""
+        return bool(self.info.flags & ED_STORED) and self.nrows == self.dim
+
+    def hxv_multi(self, X, Y=None, stream=None):
+        """Stored H applied to the nvec columns of the torch device tensor X,
+        shape (dim, nvec), float64 or complex128, contiguous (so element
+        (row, vector) lies at row*nvec + vector), nvec in {1, 2, 4, 8}
+        (ed_sector_hxv_multi): one pass over the matrix for all columns, each
+        column bit-identical to the one-pass stored H·v.  Returns Y (a new
+        tensor unless given), async on `stream`."""
+        import torch
+
+        if X.dtype not in (torch.float64, torch.complex128):
+            raise TypeError("vectors must be float64 or complex128")
+        if X.dim() != 2 or X.shape[0] != self.dim or not X.is_contiguous():
+            raise ValueError("hxv_multi: X must be a contiguous (dim, nvec) tensor")
+        if Y is None:
+            Y = torch.empty_like(X)
+        if Y.dtype != X.dtype or Y.shape != X.shape or not Y.is_contiguous():
+            raise ValueError("hxv_multi: Y must match X")
+        if stream is None:
+            stream = torch.cuda.current_stream(X.device)
+        check(_lib.load().ed_sector_hxv_multi(self._h, 1 if X.is_complex() else 0, int(X.shape[1]), _tptr(X),
+                                              _tptr(Y), _stream_ptr(stream)), "ed_sector_hxv_multi")
+        return Y
+
+    def lanc_tridiag_lockstep(self, seeds, nlanc: int, threshold: float = 1e-13):
+        """sp_lanc_tridiag of every row of the contiguous torch device tensor
+        `seeds`, shape (nseed, dim), advanced in lockstep groups of 8, 4, 2, 1
+        (ed_sector_lanc_tridiag_lockstep).  The seeds must be complete on
+        entry: the run is on the sector's own stream.  Returns (alfa, beta)
+        of shape (nseed, nlanc) and nlanc found per seed."""
+        import torch
+
+        if seeds.dtype not in (torch.float64, torch.complex128):
+            raise TypeError("vectors must be float64 or complex128")
+        if seeds.dim() != 2 or seeds.shape[1] != self.dim or not seeds.is_contiguous():
+            raise ValueError("lanc_tridiag_lockstep: seeds must be a contiguous (nseed, dim) tensor")
+        k = int(seeds.shape[0])
+        a = np.zeros((k, nlanc))
+        b = np.zeros((k, nlanc))
+        n = np.zeros(k, dtype=np.int32)
+        check(_lib.load().ed_sector_lanc_tridiag_lockstep(self._h, 1 if seeds.is_complex() else 0, k, _tptr(seeds),
+                                                          nlanc, threshold, _ptr(a), _ptr(b), _ptr(n)),
+              "ed_sector_lanc_tridiag_lockstep")
+        return a, b, n
+
     def eigh(self, neigen: int = 6, ncv: int = 23, maxit: int = 512, tol: float = 1e-12,
              v0: Optional[np.ndarray] = None, vectors: bool = True, real: Optional[bool] = None,
              on_device: bool = False):

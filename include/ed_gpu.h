@@ -493,6 +493,30 @@ int ed_sector_lanc_tridiag_dev(ed_sector* s, int32_t vtype, const void* v0_dev, 
 int ed_sector_lanc_tridiag_batch(ed_sector* s, int32_t vtype, int32_t nseed, const void* v0_dev,
                                  int32_t nitermax, double threshold, double* alfa, double* beta,
                                  int32_t* nlanc);
+/* Stored H applied to nvec vectors in one pass over the matrix (spMatVec_cc,
+ * STORED_HxV.f90:132-143, for every column): x_dev and y_dev are dim x nvec
+ * blocks interleaved by row, element (row i, vector v) at i*nvec + v, of
+ * real(8) (vtype 0) or complex(8) (vtype 1) values; nvec in {1, 2, 4, 8}.
+ * Column v of y is bit-identical to ed_sector_hxv_dev of column v on a sector
+ * with ED_OPT_STORED_EXACT.  Async on `stream`.  Refused before any launch,
+ * nothing written: ED_ERR_ARG for nvec outside the set, a null pointer, y
+ * overlapping x (x == y included), blocks not 16-byte aligned, vtype outside
+ * {0, 1} or vtype 0 on a complex H; ED_ERR_UNSUPPORTED for a sector without a
+ * stored matrix (ED_STORED) and for a row-split sector. */
+int ed_sector_hxv_multi(ed_sector* s, int32_t vtype, int32_t nvec, const void* x_dev, void* y_dev,
+                        void* stream);
+/* sp_lanc_tridiag (.repo/PLAIN_LANCZOS.f90:87-118) for nseed device start
+ * vectors advanced in lockstep: arguments and outputs as
+ * ed_sector_lanc_tridiag_batch, any nseed >= 1.  The seeds are cut into groups
+ * of 8, 4, 2, 1 whose vectors are interleaved by row; each Krylov step reads
+ * the stored H once per group (ed_sector_hxv_multi's kernel) instead of once
+ * per seed.  A seed that breaks down ends with its own nlanc while the others
+ * of its group go on.  alfa and beta agree with the batch entry's to rounding
+ * (the dot products are summed in another order), not bit for bit.  Refusals
+ * as ed_sector_hxv_multi: the sector must be stored and whole. */
+int ed_sector_lanc_tridiag_lockstep(ed_sector* s, int32_t vtype, int32_t nseed, const void* v0_dev,
+                                    int32_t nitermax, double threshold, double* alfa, double* beta,
+                                    int32_t* nlanc);
 /* GF poles of one continued fraction (host, O(n^2)): E[n] ascending eigenvalues
  * of tridiag(alfa[0:n], beta[1:n]), z2[n] the squared first components of
  * their eigenvectors and (z1 != NULL) the first components themselves, Z(1,j).
